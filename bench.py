@@ -19,8 +19,14 @@ resident in HBM) with the float32 CLIP ViT-B/32 tower, ONE all-gather of the [N/
 resident on every GPU in the global row order, then exact top-100 for the rank's shard of the queries.  Total work is
 fixed (BASELINE configs[4]'s corpus): strong scaling.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` for the dominant kernel and
-`cpu_baseline` (the oracle timed on this box's host cores; N = 1 only).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the `--steps` steps and
+reports the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`) and nothing else.  `--full` adds
+every other figure: `roofline` for the dominant kernel (per-launch events in the first timed step, socket power), the side
+configurations, the correctness checks of the retrieval line and `cpu_baseline` (the oracle timed on this box's host cores; N = 1 only).
+
+`--dump-outputs DIR` writes what the timed path returned in its last timed step (rank 0) as DIR/<name>.npy, float32 (float64 for
+integer results), at most 48 MB in all: an output that does not fit is written as a fixed, seeded sample of its flattened elements.
+The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -58,8 +64,13 @@ def parse(argv=None):
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--denoise-steps", type=int, default=30)
     ap.add_argument("--res", type=int, default=1024)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side-configs", action="store_true", help="skip the BASELINE configs[1] side measurement (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: roofline, power, side configurations, "
+                         "retrieval checks, CPU baseline (off by default: a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-side-configs", action="store_true", help="with --full: skip the side configurations (N = 1 only)")
     ap.add_argument("--roofline-every", type=int, default=5, help="bracket the GEMMs of every n-th denoise step with events")
     ap.add_argument("--corpus", type=int, default=118287, help="retrieval: corpus images in total (BASELINE configs[4])")
     ap.add_argument("--queries", type=int, default=64, help="retrieval: queries in total (sharded over ranks)")
@@ -444,15 +455,16 @@ def run_generate(args, d: Dist):
         job.run_batch()
     torch.cuda.synchronize()
     d.barrier()
-    # live per-launch timing of the dominant kernel (GEMM) with events on the launch stream: every GEMM / conv launch of
+    # --full: live per-launch timing of the dominant kernel (GEMM) with events on the launch stream: every GEMM / conv launch of
     # the prior, the VAE encodes and the decode, and of every 5th denoise step (all 30 launch the same shapes) of the
-    # first timed batch; everything else runs exactly as the product path does (hipGraph replay of the DiT forward)
-    rec = ops.GemmRecorder(every=args.roofline_every)
-    power = PowerSampler(d.local if not d.shared else 0, enabled=d.rank == 0)
+    # first timed batch; everything else runs exactly as the product path does (hipGraph replay of the DiT forward).
+    # A plain run times the product path alone.
+    rec = ops.GemmRecorder(every=args.roofline_every) if args.full else None
+    power = PowerSampler(d.local if not d.shared else 0, enabled=args.full and d.rank == 0)
     t0 = time.perf_counter()
     with power:
         for i in range(args.steps):
-            job.run_batch(recorder=rec if i == 0 else None)
+            result = job.run_batch(recorder=rec if i == 0 else None)
         torch.cuda.synchronize()
         own = time.perf_counter() - t0                  # this rank's own clock, before the closing barrier
     d.barrier()
@@ -460,7 +472,24 @@ def run_generate(args, d: Dist):
     per_rank = d.all_ranks(own)
     images = args.steps * args.batch * d.world
     if d.rank != 0:
-        return None
+        return None, None
+    outputs = {"images": result.cpu().numpy()} if args.dump_outputs else None     # uint8 [B, res, res, 3]: the composites
+    del result
+    out = {
+        "metric": f"composited images/sec @{args.res}^2, {args.denoise_steps} Flux-Redux steps", "value": images / dt, "unit": "images/s",
+        "n_gpus": d.world, "rccl_ranks": d.rccl_ranks if d.rccl_ranks is not None else 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "per_rank": {"seconds": per_rank, "images_per_s": [args.steps * args.batch / t for t in per_rank],
+                     "clock": "value uses the max-over-ranks time between the two barriers; these are each rank's own "
+                              "seconds to finish its batches (before the closing barrier)"},
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": f"Flux-Redux outpaint (Fill) {args.res}x{args.res}, {args.denoise_steps} steps, "
+                               f"batch={args.batch} per GPU (BASELINE configs[2])",
+                   "stages": job.stages(), "global_batch": args.batch * d.world, "parallelism": f"dp{d.world}",
+                   "weights": "seeded random init of the FLUX.1-Fill-dev architecture"},
+    }
+    if not args.full:
+        return out, outputs
     flops, ms, launches = rec.totals()
     all_gemm = flops / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
     bk = rec.by_kernel()                      # the dominant kernel by time: every large Linear (gemm_bf16_w4p since round 5, gemm_bf16_t256<0> before)
@@ -487,33 +516,20 @@ def run_generate(args, d: Dist):
         # energy of the timed region on rank 0's GPU: mean socket power x the region's seconds / the images this GPU produced
         pw["joules_per_image"] = pw["socket_w_mean"] * dt / (args.steps * args.batch)
         pw["joules_note"] = "mean sampled socket W x timed seconds / images of this GPU (rank 0); whole pipeline, idle gaps included"
-    out = {
-        "metric": f"composited images/sec @{args.res}^2, {args.denoise_steps} Flux-Redux steps", "value": images / dt, "unit": "images/s",
-        "n_gpus": d.world, "rccl_ranks": d.rccl_ranks if d.rccl_ranks is not None else 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3,
-        "per_rank": {"seconds": per_rank, "images_per_s": [args.steps * args.batch / t for t in per_rank],
-                     "clock": "value uses the max-over-ranks time between the two barriers; these are each rank's own "
-                              "seconds to finish its batches (before the closing barrier)"},
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-        "config": {"workload": f"Flux-Redux outpaint (Fill) {args.res}x{args.res}, {args.denoise_steps} steps, "
-                               f"batch={args.batch} per GPU (BASELINE configs[2])",
-                   "stages": job.stages(), "global_batch": args.batch * d.world, "parallelism": f"dp{d.world}",
-                   "weights": "seeded random init of the FLUX.1-Fill-dev architecture"},
-        "roofline": {"bound": "mfma", "kernel": dom, "achieved": achieved, "peak": MFMA_BF16_PEAK_TF,
-                     "unit": "TFLOP/s", "frac": achieved / MFMA_BF16_PEAK_TF, "traffic": traffic,
-                     "traffic_note": f"bytes/launch of {dom} from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes "
-                                     f"({traffic_src}); includes Infinity-Cache hits",
-                     "launches_timed": dn, "sampled": f"all non-DiT stages + every {rec.every}th denoise step of the first timed batch",
-                     "avg_launch_ms": dms / max(dn, 1),
-                     "kernel_time_share_of_gemm": dms / ms if ms > 0 else None,
-                     "all_gemm_conv_launches": {"launches": launches, "achieved": all_gemm, "avg_launch_ms": ms / max(launches, 1),
-                                                "by_kernel": {k: {"launches": v[0], "avg_launch_ms": v[1] / max(v[0], 1),
-                                                                  "achieved": v[2] / (v[1] * 1e-3) / 1e12 if v[1] > 0 else 0.0}
-                                                              for k, v in bk.items()}},
-                     "e2e_mfma_frac": job.flops_per_image() * images / d.world / dt / (MFMA_BF16_PEAK_TF * 1e12),
-                     "attention": attention,
-                     "mfma_util_pmc": _pmc_mfma_util(), "power": pw},
-    }
+    out["roofline"] = {"bound": "mfma", "kernel": dom, "achieved": achieved, "peak": MFMA_BF16_PEAK_TF,
+                        "unit": "TFLOP/s", "frac": achieved / MFMA_BF16_PEAK_TF, "traffic": traffic,
+                        "traffic_note": f"bytes/launch of {dom} from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes "
+                                        f"({traffic_src}); includes Infinity-Cache hits",
+                        "launches_timed": dn, "sampled": f"all non-DiT stages + every {rec.every}th denoise step of the first timed batch",
+                        "avg_launch_ms": dms / max(dn, 1),
+                        "kernel_time_share_of_gemm": dms / ms if ms > 0 else None,
+                        "all_gemm_conv_launches": {"launches": launches, "achieved": all_gemm, "avg_launch_ms": ms / max(launches, 1),
+                                                   "by_kernel": {k: {"launches": v[0], "avg_launch_ms": v[1] / max(v[0], 1),
+                                                                     "achieved": v[2] / (v[1] * 1e-3) / 1e12 if v[1] > 0 else 0.0}
+                                                                 for k, v in bk.items()}},
+                        "e2e_mfma_frac": job.flops_per_image() * images / d.world / dt / (MFMA_BF16_PEAK_TF * 1e12),
+                        "attention": attention,
+                        "mfma_util_pmc": _pmc_mfma_util(), "power": pw}
     if not args.no_side_configs and d.world == 1:
         del job
         torch.cuda.empty_cache()
@@ -524,7 +540,7 @@ def run_generate(args, d: Dist):
         out["side_configs"]["retrieval"] = side_retrieval(d.dev, cpu_budget_s=0.0 if args.no_cpu_baseline else 10.0)
     if not args.no_cpu_baseline and d.world == 1:
         out["cpu_baseline"] = cpu_baseline_generate(args.res, args.denoise_steps)
-    return out
+    return out, outputs
 
 
 def side_config1(dev) -> dict:
@@ -703,19 +719,24 @@ def run_retrieval(args, d: Dist):
     ev = lambda: torch.cuda.Event(enable_timing=True)                             # noqa: E731
 
     def step(timers=None, rec=None):
-        t = [ev() for _ in range(4)]
-        t[0].record()
+        t = [ev() for _ in range(4)] if timers is not None else None          # stage events: --full only
+
+        def mark(j):
+            if t is not None:
+                t[j].record()
+
+        mark(0)
         ops.set_recorder(rec)
         try:
             local = embed_images(model, crops, args.embed_batch)
         finally:
             ops.set_recorder(None)
-        t[1].record()
+        mark(1)
         corpus = allgather_rows(local, N)
-        t[2].record()
+        mark(2)
         queries = (corpus[planted[qs:qe]] + qnoise[qs:qe]).contiguous()
         D, I = ops.cosine_topk(corpus, queries, k) if qe > qs else (None, None)
-        t[3].record()
+        mark(3)
         if timers is not None:
             timers.append(t)
         return corpus, queries, D, I
@@ -724,14 +745,34 @@ def run_retrieval(args, d: Dist):
         step()
     torch.cuda.synchronize()
     d.barrier()
-    timers: list = []
-    rec = ops.GemmRecorder(f32=True) if args.clip_precision == "fp32" else ops.GemmRecorder()
+    timers: list | None = [] if args.full else None
+    rec = None
+    if args.full:
+        rec = ops.GemmRecorder(f32=True) if args.clip_precision == "fp32" else ops.GemmRecorder()
     t0 = time.perf_counter()
     for i in range(args.steps):
         corpus, queries, D, I = step(timers, rec if i == 0 else None)
     torch.cuda.synchronize()
     d.barrier()
     dt = d.max_over_ranks(time.perf_counter() - t0)
+    outputs = None
+    if d.rank == 0 and args.dump_outputs:
+        # what a caller of the step receives on rank 0: the all-gathered corpus embeddings, this rank's queries and their top-k
+        outputs = {"corpus_embeddings": corpus.cpu().numpy(), "queries": queries.cpu().numpy()}
+        if D is not None:
+            outputs.update(topk_scores=D.cpu().numpy(), topk_indices=I.cpu().numpy())
+    out = {
+        "metric": f"corpus images/sec through embed + all-gather + top-{k} (CLIP ViT-B/32, N={N})", "value": args.steps * N / dt,
+        "unit": "images/s", "n_gpus": d.world, "rccl_ranks": d.rccl_ranks if d.rccl_ranks is not None else 1, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "f32" if args.clip_precision == "fp32" else "bf16", "data": "synthetic",
+        "config": {"workload": f"retrieval: {N} synthetic 224^2 uint8 crops resident in HBM -> CLIP ViT-B/32 ({args.clip_precision}) -> "
+                               f"unit-norm f32 [N,512], rank-sharded; one all-gather; exact top-{k} of {Q} queries (BASELINE configs[4] corpus)",
+                   "corpus": N, "queries": Q, "k": k, "embed_batch": args.embed_batch, "parallelism": f"corpus-shard{d.world}",
+                   "weights": "seeded random init of the CLIP ViT-B/32 architecture"},
+    }
+    if not args.full:
+        return (out, outputs) if d.rank == 0 else (None, None)
     # checks (outside the timed region): planted neighbours come back first on this rank's queries
     hits = int((I[:, 0] == planted[qs:qe]).sum().item()) if qe > qs else 0
     # the HBM-bound scan kernel alone, events on the launch stream
@@ -751,7 +792,7 @@ def run_retrieval(args, d: Dist):
     torch.cuda.synchronize()
     scan_ms, topk_ms = e0.elapsed_time(e1) / reps, f0.elapsed_time(f1) / reps
     if d.rank != 0:
-        return None
+        return None, None
     qn = q16.shape[0]
     scan_bytes = N * 512 * 4 + qn * 512 * 4 + qn * ((N + 63) // 64 * 64) * 4        # corpus + queries read, score rows written
     topk_bytes = N * 512 * 4 + qn * 512 * 4 + qn * k * 12                             # SURVEY §8(d) formula
@@ -761,15 +802,7 @@ def run_retrieval(args, d: Dist):
     cap = shard_bounds(N, d.world, 0)[1]
     ag_bytes = (d.world - 1) * cap * 512 * 4                      # what one GPU receives: the other ranks' padded shards
     flops, ms, launches = rec.totals()
-    out = {
-        "metric": f"corpus images/sec through embed + all-gather + top-{k} (CLIP ViT-B/32, N={N})", "value": args.steps * N / dt,
-        "unit": "images/s", "n_gpus": d.world, "rccl_ranks": d.rccl_ranks if d.rccl_ranks is not None else 1, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": "f32" if args.clip_precision == "fp32" else "bf16", "data": "synthetic",
-        "config": {"workload": f"retrieval: {N} synthetic 224^2 uint8 crops resident in HBM -> CLIP ViT-B/32 ({args.clip_precision}) -> "
-                               f"unit-norm f32 [N,512], rank-sharded; one all-gather; exact top-{k} of {Q} queries (BASELINE configs[4] corpus)",
-                   "corpus": N, "queries": Q, "k": k, "embed_batch": args.embed_batch, "parallelism": f"corpus-shard{d.world}",
-                   "weights": "seeded random init of the CLIP ViT-B/32 architecture"},
+    out.update({
         "stage_ms": {"embed_shard": emb_ms, "all_gather": ag_ms, "topk_shard_of_queries": tk_ms},
         "planted_neighbour_first": f"{hits}/{qe - qs} on rank 0's query shard",
         "roofline": {"bound": "hbm", "kernel": "ip_scan_kernel", "achieved": scan_bytes / (scan_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
@@ -792,14 +825,39 @@ def run_retrieval(args, d: Dist):
                       "achieved": ag_bytes / (ag_ms * 1e-3) / 1e9 if d.world > 1 and ag_ms > 0 else None, "unit": "GB/s",
                       "peak": XGMI_LINKS * XGMI_LINK_GBS, "note": "one all_gather_into_tensor of zero-padded [ceil(N/W), 512] f32 shards "
                                                                    "(RCCL over xGMI); single rank: no collective"},
-    }
+    })
     if not args.no_cpu_baseline and d.world == 1:
         out["cpu_baseline"] = cpu_baseline_retrieval(k)
-    return out
+    return out, outputs
+
+
+# ----------------------------------------------------------------------------------------------- outputs
+DUMP_BYTES = 48 << 20          # all .npy files of one --dump-outputs together
+
+
+def dump_outputs(outdir: str, arrays: dict) -> None:
+    """DIR/<name>.npy per output: float32, float64 for integer results (exact).  The budget is shared out smallest first; an output
+    that does not fit its share is written as a seeded sample of its flattened elements (the same indices on every run)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    left = DUMP_BYTES
+    items = sorted(arrays.items(), key=lambda kv: kv[1].size)
+    for i, (name, a) in enumerate(items):
+        dt = np.float64 if a.dtype.kind in "iu" and a.dtype.itemsize > 2 else np.float32
+        cap = left // (len(items) - i) // np.dtype(dt).itemsize
+        flat = a.reshape(-1)
+        if flat.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(flat.size, size=cap, replace=False))
+            a = flat[idx]
+        a = np.ascontiguousarray(a, dtype=dt)
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def main():
     args = parse()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
     self_launch_if_needed(args)
     d = Dist(args)
     try:
@@ -810,8 +868,10 @@ def main():
         if d.rank == 0:
             ge.build()
         d.barrier()
-        out = run_generate(args, d) if args.workload == "generate" else run_retrieval(args, d)
+        out, outputs = run_generate(args, d) if args.workload == "generate" else run_retrieval(args, d)
         if d.rank == 0:
+            if outputs is not None:
+                dump_outputs(args.dump_outputs, outputs)
             if d.shared:
                 out["debug_share_gpu"] = "all ranks on GPU 0 over gloo: control-flow check only, NOT a measurement"
             print(json.dumps(out), flush=True)
