@@ -42,6 +42,9 @@ def build_parser():
                    help="the reference's hard-coded coco_dataset_dir (batch_…:29)")
     p.add_argument("--synthetic-weights", action="store_true")
     p.add_argument("--tiny", action="store_true", help="test hook: tiny architectures, small images")
+    p.add_argument("--text_encoder", choices=["transformers", "hip"], default="transformers",
+                   help="what encodes a prompt without a prompt_cache file: the transformers T5 / CLIP modules (eager torch) or the HIP "
+                        "encoders (domain_rag_amd.textenc); tokenizers are host Python either way")
     p.add_argument("--num_inference_steps", type=int, default=STEPS)
     p.add_argument("--size", type=int, default=SIZE)
     p.add_argument("--io_workers", type=int, default=4, help="background PNG encoder processes (0 = write inline like the reference)")
@@ -270,7 +273,8 @@ def main(argv=None):
         results = json.load(f)
     from ..io_pool import ImageWriter
     args.writer = ImageWriter(args.io_workers)
-    engine = Engine("dev", args.model_root, synthetic=args.synthetic_weights, tiny=args.tiny, device=torch.device("cuda", local))
+    engine = Engine("dev", args.model_root, synthetic=args.synthetic_weights, tiny=args.tiny, device=torch.device("cuda", local),
+                    text_encoder=args.text_encoder)
     datasets = [args.dataset] if args.dataset else (DATASET_GROUPS[args.dataset_group] if args.dataset_group else list(results))
     tot_ok = tot_bad = 0
     for ds in datasets:

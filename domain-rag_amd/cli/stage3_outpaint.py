@@ -55,6 +55,9 @@ def build_parser():
     p.add_argument("--datasets_dir", type=str, default=DATASETS_DIR)
     p.add_argument("--synthetic-weights", action="store_true")
     p.add_argument("--tiny", action="store_true", help="test hook: tiny architectures, min_dimension 64")
+    p.add_argument("--text_encoder", choices=["transformers", "hip"], default="transformers",
+                   help="what encodes a prompt without a prompt_cache file: the transformers T5 / CLIP modules (eager torch) or the HIP "
+                        "encoders (domain_rag_amd.textenc); tokenizers are host Python either way")
     p.add_argument("--num_inference_steps", type=int, default=H.NUM_INFERENCE_STEPS)
     p.add_argument("--io_workers", type=int, default=4, help="background PNG encoder processes (0 = write inline like the reference)")
     p.add_argument("--png", choices=["gpu", "host"], default="gpu",
@@ -263,7 +266,8 @@ def collect_final_results(process_id, shot, source_process_id=None):
 def run_rank(args, datasets, process_id, rank, world, gpu_process_id=None):
     local = int(os.environ.get("LOCAL_RANK", str(rank))) % max(torch.cuda.device_count(), 1)   # (more ranks than GPUs: share them)
     torch.cuda.set_device(local)
-    engine = Engine("fill", args.model_root, synthetic=args.synthetic_weights, tiny=args.tiny, device=torch.device("cuda", local))
+    engine = Engine("fill", args.model_root, synthetic=args.synthetic_weights, tiny=args.tiny, device=torch.device("cuda", local),
+                    text_encoder=args.text_encoder)
     rng = random.Random(None if args.seed is None else args.seed + rank)
     writer = ImageWriter(args.io_workers)
     done, failed = parse_resume_log(args.log_file) if (args.resume or args.failed_only) else (set(), set())

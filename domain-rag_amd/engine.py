@@ -5,7 +5,9 @@ HIP classes, or build seeded synthetic weights of the same architectures when no
 sample at outpainting_…:1185 — a pure slowdown).
 
 Text encoders: the prompt is constant per dataset ("" everywhere except FISH, outpainting_…:85-95), so T5 /
-CLIP-text outputs are cached inputs (``prompt_embeds_cache``), never on the per-image path.
+CLIP-text outputs are cached inputs (``prompt_embeds_cache``), never on the per-image path.  A cache miss is encoded by the
+``transformers`` modules (``text_encoder="transformers"``, the default) or by the HIP encoders of :mod:`.textenc`
+(``text_encoder="hip"``); the tokenizers are the reference's host tokenizers either way.
 """
 from __future__ import annotations
 
@@ -75,10 +77,44 @@ def encode_prompt_with(text_encoder, text_encoder_2, tokenizer, tokenizer_2, pro
 def load_text_encoders(flux_dir: str, device="cuda"):
     """the four objects the reference's ``load_model`` builds from ``<model>/FLUX.1-*/{text_encoder, text_encoder_2,
     tokenizer, tokenizer_2}`` (batch_…:120-137), bf16"""
-    from transformers import CLIPTextModel, CLIPTokenizer, T5EncoderModel, T5TokenizerFast
+    from transformers import CLIPTextModel, T5EncoderModel
     te = CLIPTextModel.from_pretrained(flux_dir, subfolder="text_encoder", torch_dtype=torch.bfloat16).to(device).eval()
     te2 = T5EncoderModel.from_pretrained(flux_dir, subfolder="text_encoder_2", torch_dtype=torch.bfloat16).to(device).eval()
-    return te, te2, CLIPTokenizer.from_pretrained(flux_dir, subfolder="tokenizer"), T5TokenizerFast.from_pretrained(flux_dir, subfolder="tokenizer_2")
+    return (te, te2) + tuple(load_tokenizers(flux_dir))
+
+
+def load_tokenizers(flux_dir: str):
+    """``<flux_dir>/{tokenizer, tokenizer_2}``: the reference's CLIPTokenizer / T5TokenizerFast (host Python)"""
+    from transformers import CLIPTokenizer, T5TokenizerFast
+    return CLIPTokenizer.from_pretrained(flux_dir, subfolder="tokenizer"), T5TokenizerFast.from_pretrained(flux_dir, subfolder="tokenizer_2")
+
+
+def load_text_encoders_hip(flux_dir: str, device="cuda"):
+    """``load_text_encoders`` with the two encoders on the HIP path (:class:`.textenc.ClipTextHIP`, :class:`.textenc.T5EncoderHIP`,
+    bf16 from the same ``text_encoder`` / ``text_encoder_2`` directories)"""
+    from .textenc import ClipTextHIP, T5EncoderHIP
+    te = ClipTextHIP.from_pretrained(os.path.join(flux_dir, "text_encoder"), device)
+    te2 = T5EncoderHIP.from_pretrained(os.path.join(flux_dir, "text_encoder_2"), device)
+    return (te, te2) + tuple(load_tokenizers(flux_dir))
+
+
+def synthetic_text_encoders_hip(tiny: bool, J: int, P: int, seed: int, device="cuda"):
+    """seeded HIP encoders for ``synthetic=True`` runs (there are no checkpoints offline): FLUX.1's architectures, or tiny ones whose widths
+    are the tiny transformer's joint_attention_dim ``J`` / pooled_projection_dim ``P``; with :class:`.textenc.StandInTokenizer`s (prompt bytes
+    as ids — no tokenizer files exist for synthetic runs either)"""
+    from .textenc import ClipTextConfig, ClipTextHIP, StandInTokenizer, T5EncoderConfig, T5EncoderHIP
+    if tiny:
+        ccfg = ClipTextConfig(vocab_size=256, hidden_size=P, intermediate_size=2 * P, num_hidden_layers=1, num_attention_heads=P // 64)
+        tcfg = T5EncoderConfig(vocab_size=256, d_model=J, d_ff=2 * J, num_layers=1, num_heads=J // 64)
+    else:
+        ccfg, tcfg = ClipTextConfig(), T5EncoderConfig()
+    te = ClipTextHIP.synthetic(ccfg, seed, device)
+    te2 = T5EncoderHIP.synthetic(tcfg, seed + 1, device)
+    # CLIP: bos / eos = the two largest ids (eos_token_id == 2 configs pool at argmax(ids)), padded with eos; T5: eos 1, pad 0
+    tok = StandInTokenizer(ccfg.vocab_size, ccfg.max_position_embeddings, eos_id=ccfg.vocab_size - 1, pad_id=ccfg.vocab_size - 1,
+                           bos_id=ccfg.vocab_size - 2)
+    tok2 = StandInTokenizer(tcfg.vocab_size, redux_mod.T5_TOKENS, eos_id=1, pad_id=0)
+    return te, te2, tok, tok2
 
 
 class TextCache:
@@ -86,10 +122,11 @@ class TextCache:
     the caller's text encoders if given (``encoders`` = (text_encoder, text_encoder_2, tokenizer, tokenizer_2), result
     written back to the cache file); synthetic mode derives seeded stand-ins from the prompt hash."""
 
-    def __init__(self, model_root: str, synthetic: bool, Lt: int, J: int, P: int, device, encoders=None, loader=None):
+    def __init__(self, model_root: str, synthetic: bool, Lt: int, J: int, P: int, device, encoders=None, loader=None, persist: bool = True):
         self.root, self.synthetic, self.Lt, self.J, self.P, self.dev = model_root, synthetic, Lt, J, P, device
         self.encoders = encoders if encoders is not None and all(e is not None for e in encoders) else None
         self.loader = loader            # () -> encoders tuple, called on the first cache miss only (T5-XXL is 9.5 GB)
+        self.persist = persist          # False: encodings stay in memory (encoders with seeded stand-in weights)
         self._mem: dict = {}
 
     def get(self, prompt: str, prompt_2: str = ""):
@@ -104,6 +141,8 @@ class TextCache:
                     self.encoders = self.loader()
                 t5, pooled = encode_prompt_with(*self.encoders, prompt, prompt_2, self.Lt)
                 try:
+                    if not self.persist:
+                        raise OSError("encoders with synthetic weights: kept in memory")
                     os.makedirs(os.path.dirname(path), exist_ok=True)
                     torch.save({"prompt": prompt, "prompt_2": prompt_2, "prompt_embeds": t5.to(torch.bfloat16),
                                 "pooled_prompt_embeds": pooled.to(torch.bfloat16)}, path)
@@ -157,8 +196,12 @@ class Engine:
     """Everything stage 2 / stage 3 need, loaded once."""
 
     def __init__(self, kind: str, model_root: str = "./model", synthetic: bool = False, tiny: bool = False, device="cuda",
-                 seed: int = 0):
+                 seed: int = 0, text_encoder: str = "transformers"):
+        """``text_encoder``: what encodes a prompt-cache miss — "transformers" (the reference's modules, eager torch) or "hip"
+        (:mod:`.textenc`; with ``synthetic``: seeded encoders and stand-in tokenizers, results kept in memory)"""
         assert kind in ("dev", "fill")
+        if text_encoder not in ("transformers", "hip"):
+            raise ValueError(f"text_encoder must be 'transformers' or 'hip', not {text_encoder!r}")
         dev = torch.device(device)
         self.dev, self.kind = dev, kind
         fkw = dict(TINY["flux"]) if tiny else {}
@@ -187,9 +230,14 @@ class Engine:
         self.cfg, self.vit_cfg = cfg, vitcfg
         self.prior = redux_mod.ReduxPriorHIP(vitcfg, vitp, rp, dev)
         self.pipe = FluxFillHIP(tr, vae) if kind == "fill" else FluxTxt2ImgHIP(tr, vae)
-        self.text = TextCache(model_root, synthetic, TINY["t5_tokens"] if tiny else redux_mod.T5_TOKENS, cfg.joint_attention_dim,
-                              cfg.pooled_projection_dim, dev,
-                              loader=(lambda: load_text_encoders(flux_dir, dev)) if os.path.isdir(os.path.join(flux_dir, "text_encoder_2")) else None)
+        Lt, J, P = TINY["t5_tokens"] if tiny else redux_mod.T5_TOKENS, cfg.joint_attention_dim, cfg.pooled_projection_dim
+        if text_encoder == "hip" and synthetic:
+            self.text = TextCache(model_root, False, Lt, J, P, dev, persist=False,
+                                  loader=lambda: synthetic_text_encoders_hip(tiny, J, P, seed + 4, dev))
+        else:
+            load = load_text_encoders_hip if text_encoder == "hip" else load_text_encoders
+            self.text = TextCache(model_root, synthetic, Lt, J, P, dev,
+                                  loader=(lambda: load(flux_dir, dev)) if os.path.isdir(os.path.join(flux_dir, "text_encoder_2")) else None)
 
     def prior_embeds(self, pil_images, prompt: str, embeds_scale, pooled_scale):
         """pipe_prior_redux(images, prompt=…, prompt_2="", prompt_embeds_scale=…, pooled_prompt_embeds_scale=…)"""

@@ -716,3 +716,85 @@ def clip_embed_ln(emb, cls, pos, gamma, beta, x, B: int, T: int, D: int, eps: fl
 
 def attention_small_f32(qkv, out, B: int, T: int, H: int, hd: int, ld: int, ldo: int, scale: float) -> None:
     check(_lib.load().drag_attention_small_f32(_p(qkv), _p(out), B, T, H, hd, ld, ldo, scale, _stream()), "drag_attention_small_f32")
+
+
+def _room(t: torch.Tensor) -> int:
+    """elements of ``t``'s storage from its first element on"""
+    return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+
+
+def textenc_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, B: int, S: int, H: int, *, ld: int,
+                      batch_stride: int, scale: float, rel_bias: torch.Tensor | None = None, causal: bool = False, eager: bool,
+                      ld_o: int | None = None, o_batch_stride: int | None = None) -> torch.Tensor:
+    """head_dim-64 attention of the prompt encoders (``drag_textenc_attention_bf16``): ``q`` / ``k`` / ``v`` are views whose first element is
+    head 0 of token 0 of batch 0 (token s of batch b at + b * batch_stride + s * ld, head h at + 64 h), ``out`` [B, S, H*64] rows of ``ld_o``.
+    ``rel_bias`` bf16 [H, 2S-1] (T5), ``causal`` (CLIP); ``eager`` = T5's eager numerics, else CLIP's SDPA numerics."""
+    lib = _lib.load()
+    for t, n in ((q, "q"), (k, "k"), (v, "v"), (out, "out")):
+        _need(t, torch.bfloat16, f"textenc_attention.{n}")
+    ld_o = H * 64 if ld_o is None else ld_o
+    o_batch_stride = S * ld_o if o_batch_stride is None else o_batch_stride
+    span = (B - 1) * batch_stride + (S - 1) * ld + H * 64
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        if span > _room(t):
+            raise ValueError(f"textenc_attention.{n}: {B} x {S} rows of stride {ld} / {batch_stride} do not fit the buffer")
+    if (B - 1) * o_batch_stride + (S - 1) * ld_o + H * 64 > _room(out):
+        raise ValueError("textenc_attention.out: the output rows do not fit the destination")
+    if rel_bias is not None:
+        _need(rel_bias, torch.bfloat16, "textenc_attention.rel_bias")
+        if tuple(rel_bias.shape) != (H, 2 * S - 1) or not rel_bias.is_contiguous():
+            raise ValueError(f"textenc_attention.rel_bias: expected a contiguous [{H}, {2 * S - 1}] table, got {tuple(rel_bias.shape)}")
+    check(lib.drag_textenc_attention_bf16(_p(q), _p(k), _p(v), _p(out), B, S, H, ld, batch_stride, ld_o, o_batch_stride, float(scale),
+                                          _p(rel_bias), int(causal), int(eager), _stream()), "drag_textenc_attention_bf16")
+    return out
+
+
+def t5_rmsnorm(x: torch.Tensor, weight: torch.Tensor, out: torch.Tensor, eps: float) -> torch.Tensor:
+    """T5LayerNorm of the dense rows of ``x`` [M, D] into ``out`` (``drag_t5_rmsnorm_bf16``)"""
+    for t, n in ((x, "x"), (weight, "weight"), (out, "out")):
+        _need(t, torch.bfloat16, f"t5_rmsnorm.{n}")
+    D = weight.numel()
+    if not (x.is_contiguous() and out.is_contiguous() and x.numel() % D == 0 and out.numel() == x.numel()):
+        raise ValueError(f"t5_rmsnorm: x / out must be contiguous rows of {D} elements")
+    check(_lib.load().drag_t5_rmsnorm_bf16(_p(x), _p(weight), _p(out), x.numel() // D, D, float(eps), _stream()), "drag_t5_rmsnorm_bf16")
+    return out
+
+
+def gated_new_gelu(h: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """``out`` [M, F] = NewGELU(h[:, :F]) * h[:, F:] of the fused wi_0 | wi_1 rows ``h`` [M, 2F] (``drag_gated_new_gelu_bf16``)"""
+    _need(h, torch.bfloat16, "gated_new_gelu.h")
+    _need(out, torch.bfloat16, "gated_new_gelu.out")
+    M, F = out.shape
+    if not (h.is_contiguous() and out.is_contiguous() and tuple(h.shape) == (M, 2 * F)):
+        raise ValueError(f"gated_new_gelu: expected contiguous h [{M}, {2 * F}] and out [{M}, {F}], got {tuple(h.shape)}")
+    check(_lib.load().drag_gated_new_gelu_bf16(_p(h), _p(out), M, F, _stream()), "drag_gated_new_gelu_bf16")
+    return out
+
+
+def quick_gelu(x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """CLIP's QuickGELU in torch's bf16 op order (``drag_quick_gelu_bf16``); ``out`` may be ``x``"""
+    _need(x, torch.bfloat16, "quick_gelu.x")
+    out = torch.empty_like(x) if out is None else out
+    _need(out, torch.bfloat16, "quick_gelu.out")
+    if not (x.is_contiguous() and out.is_contiguous() and out.numel() == x.numel()):
+        raise ValueError("quick_gelu: x / out must be contiguous tensors of the same size")
+    check(_lib.load().drag_quick_gelu_bf16(_p(x), _p(out), x.numel(), _stream()), "drag_quick_gelu_bf16")
+    return out
+
+
+def embed_gather(ids: torch.Tensor, table: torch.Tensor, out: torch.Tensor, pos: torch.Tensor | None = None) -> torch.Tensor:
+    """``out`` [B*S, D] = table[ids] (+ pos[s], one bf16 add) for int64 device ids [B, S] (``drag_embed_gather_bf16``).  The ids must lie
+    in [0, vocab): the caller checks them on the host before they are uploaded (the kernel writes a zero row for any other id)."""
+    _need(ids, torch.int64, "embed_gather.ids")
+    _need(table, torch.bfloat16, "embed_gather.table")
+    _need(out, torch.bfloat16, "embed_gather.out")
+    B, S = ids.shape
+    V, D = table.shape
+    if not (ids.is_contiguous() and table.is_contiguous() and out.is_contiguous() and out.numel() == B * S * D):
+        raise ValueError(f"embed_gather: expected contiguous ids [B, S], table [V, D] and out [{B * S}, {D}]")
+    if pos is not None:
+        _need(pos, torch.bfloat16, "embed_gather.pos")
+        if not pos.is_contiguous() or pos.shape[-1] != D or pos.numel() < S * D:
+            raise ValueError(f"embed_gather.pos: expected contiguous rows of {D} covering {S} positions")
+    check(_lib.load().drag_embed_gather_bf16(_p(ids), _p(table), _p(pos), _p(out), B * S, S, D, V, _stream()), "drag_embed_gather_bf16")
+    return out

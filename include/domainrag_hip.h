@@ -456,6 +456,35 @@ int drag_png_plan(int32_t n, int32_t H, int32_t W, int32_t C, int64_t* workspace
 int drag_png_encode(const void* images, int32_t n, int32_t H, int32_t W, int32_t C, void* workspace, int64_t workspace_bytes,
                     void* out, int64_t out_stride, int64_t* sizes, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Prompt encoders (T5-XXL encoder, CLIP-L text tower; reached from pipe_prior_redux(...) at batch_generate_flux_kshot.py:459-465 /
+ * outpainting_updown_sampling_redux.py:1237-1243 on a prompt-cache miss).  Every Linear is drag_gemm_bf16; these are the rest.
+ *
+ * drag_textenc_attention_bf16 — softmax(q k^T [*scale] [+ bias] [causal]) v over head_dim 64, out [B, S, H*64] rows of ld_o.
+ *   q, k, v: head h of token s of batch b at x + b*batch_stride + s*ld + h*64 (read in place from a fused q|k|v projection);
+ *   ld % 8 == 0, batch_stride % 8 == 0, 16-byte aligned.  1 <= S <= 512; the tail of the last key / query tile is masked.
+ *   rel_bias: NULL or bf16 [H, 2S-1], bias(h, q, k) = rel_bias[h][k - q + S - 1] (T5's bucketed relative-position bias, one
+ *   Toeplitz row per head).  causal != 0: key k > query q is masked (CLIP).
+ *   eager != 0 (T5, transformers' eager attention): s = bf16(q.k), bf16(s * scale) when scale != 1, bf16(s + bias); softmax in fp32,
+ *   P rounded to bf16 after normalisation; out = bf16(P.V).
+ *   eager == 0 (CLIP, SDPA): fp32 scores s = q.k * scale (+ bias), p = bf16(exp(s - max)), out = bf16(P.V / sum).
+ * drag_t5_rmsnorm_bf16 — T5LayerNorm over dense rows [M, D]: y = bf16(weight * bf16(x * rsqrt(mean(x^2) + eps))), fp32 mean;
+ *   D % 8 == 0, D <= 4096.
+ * drag_gated_new_gelu_bf16 — h [M, 2F] (wi_0 | wi_1 outputs) -> y [M, F] = NewGELU(h[:, :F]) * h[:, F:], every op of
+ *   NewGELUActivation a bf16 tensor op as torch evaluates it (pow(x, 3) = bf16(bf16(x x) x)); F % 8 == 0.
+ * drag_quick_gelu_bf16 — y = x * sigmoid(1.702 x) over n bf16 elements (n % 8 == 0, y may be x), each op rounded to bf16 as CLIP's
+ *   eager graph rounds it (the GEMM epilogue's DRAG_ACT_QUICK_GELU rounds once).
+ * drag_embed_gather_bf16 — out[r] = table[ids[r]] (+ pos[r % S], bf16 add: CLIP's position embedding), r < rows; ids int64 on the
+ *   device; D % 8 == 0; an id outside [0, vocab) yields a zero row (callers validate ids before the launch). */
+int drag_textenc_attention_bf16(const void* q, const void* k, const void* v, void* out, int32_t B, int32_t S, int32_t H, int32_t ld,
+                                int64_t batch_stride, int32_t ld_o, int64_t o_batch_stride, float scale, const void* rel_bias,
+                                int32_t causal, int32_t eager, void* stream);
+int drag_t5_rmsnorm_bf16(const void* x, const void* weight, void* y, int32_t M, int32_t D, float eps, void* stream);
+int drag_gated_new_gelu_bf16(const void* h, void* y, int64_t M, int32_t F, void* stream);
+int drag_quick_gelu_bf16(const void* x, void* y, int64_t n, void* stream);
+int drag_embed_gather_bf16(const int64_t* ids, const void* table, const void* pos, void* out, int64_t rows, int32_t S, int32_t D,
+                           int64_t vocab, void* stream);
+
 /* Host-side batch file reader feeding drag_jpeg_* (no device work): native threads do the per-file system calls that cost the
  * interpreter ~80 us each.  drag_file_sizes: sizes[i] = bytes of paths[i] or -errno.  drag_read_files: paths[i] -> dst[offsets[i]
  * .. offsets[i+1]) in plain host (ideally pinned) memory; status[i] = 0, errno, or -1 for a file shorter than its slot. */
