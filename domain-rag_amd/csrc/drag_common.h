@@ -86,12 +86,48 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
-// tuning switches (capi.hip): read once from the environment, changeable through drag_set_option
-enum { DRAG_OPT_ATTN_SCHED = 0, DRAG_OPT_ATTN_W4 = 1, DRAG_OPT_ATTN_TUNE = 2, DRAG_OPT_ATTN_Q64 = 3, DRAG_OPT_GEMM_KERNEL = 4, DRAG_OPT_LN_GENERIC = 5, DRAG_OPT_GEMM_GROUP_M = 6, DRAG_OPT_TOPK_GRID = 7, DRAG_OPT_TOPK_DEPTH = 8, DRAG_OPT_ATTN_PERSIST = 9, DRAG_OPT_TOPK_SELECT = 10, DRAG_OPT_TOPK_DENSE_SAMPLE = 11, DRAG_OPT_TOPK_QT = 12, DRAG_OPT_GEMM_PAIR = 13, DRAG_OPT_GEMM_EPILOGUE = 14, DRAG_OPT_TOPK_PATH = 15, DRAG_OPT_TOPK_QREG = 16, DRAG_OPT_GEMM_W4 = 17, DRAG_OPT_ATTN_WALK = 18, DRAG_OPT_GEMM_SPLITK = 19, DRAG_OPT_ATTN_GEN = 20, DRAG_OPT_COUNT = 21 };
-// measured defaults (scripts/bench_attn.py, B=8 S=5337: schedule 0 1112, 1 1139, 2 1165 TFLOP/s; 16-byte epilogue stores +0.1 % there,
+// Tuning switches: THE table.  One row per switch: X(identifier, name, default, experiment) — experiment: DRAG_OPT_PRODUCT = every value
+// exists in the product library, DRAG_OPT_EXP_ANY = every value but 0 needs a DRAG_EXPERIMENTS build, n > 0 = the value n does.  capi.hip
+// generates the rest from it: the name array, the initial values ($DRAG_ + the upper-cased name; unset = the default), the experiment
+// refusal and the "unknown option" message of drag_set_option.  Every switch is read per launch with drag_opt(DRAG_OPT_<identifier>);
+// include/domainrag_hip.h (drag_set_option) says what the values mean.
+// Measured defaults (scripts/bench_attn.py, B=8 S=5337: schedule 0 1112, 1 1139, 2 1165 TFLOP/s; 16-byte epilogue stores +0.1 % there,
 // +4...7 % at S = 1753 / 729; static wave priority: no gain, -5 % on short sequences).  All settings give the same bits.
-#define DRAG_ATTN_SCHED_DEFAULT 2
-#define DRAG_ATTN_TUNE_DEFAULT 2
+#define DRAG_OPT_PRODUCT 0
+#define DRAG_OPT_EXP_ANY (-1)
+#define DRAG_OPTIONS(X)                                     \
+  X(ATTN_SCHED, "attn_sched", 2, 3)                         \
+  X(ATTN_W4, "attn_w4", 0, DRAG_OPT_PRODUCT)                \
+  X(ATTN_TUNE, "attn_tune", 2, DRAG_OPT_PRODUCT)            \
+  X(ATTN_Q64, "attn_q64", 0, DRAG_OPT_PRODUCT)              \
+  X(GEMM_KERNEL, "gemm_kernel", 0, DRAG_OPT_PRODUCT)        \
+  X(LN_GENERIC, "ln_generic", 0, DRAG_OPT_PRODUCT)          \
+  X(GEMM_GROUP_M, "gemm_group_m", 0, DRAG_OPT_PRODUCT)      \
+  X(TOPK_GRID, "topk_grid", 0, DRAG_OPT_PRODUCT)            \
+  X(TOPK_DEPTH, "topk_depth", 0, DRAG_OPT_PRODUCT)          \
+  X(ATTN_PERSIST, "attn_persist", 0, DRAG_OPT_EXP_ANY)      \
+  X(TOPK_SELECT, "topk_select", 0, DRAG_OPT_PRODUCT)        \
+  X(TOPK_DENSE_SAMPLE, "topk_dense_sample", 0, DRAG_OPT_PRODUCT) \
+  X(TOPK_QT, "topk_qt", 0, DRAG_OPT_EXP_ANY)                \
+  X(GEMM_PAIR, "gemm_pair", 0, DRAG_OPT_PRODUCT)            \
+  X(GEMM_EPILOGUE, "gemm_epilogue", 0, DRAG_OPT_PRODUCT)    \
+  X(TOPK_PATH, "topk_path", 0, DRAG_OPT_PRODUCT)            \
+  X(TOPK_QREG, "topk_qreg", 0, DRAG_OPT_PRODUCT)            \
+  X(GEMM_W4, "gemm_w4", 0, DRAG_OPT_PRODUCT)                \
+  X(ATTN_WALK, "attn_walk", 0, DRAG_OPT_PRODUCT)            \
+  X(GEMM_SPLITK, "gemm_splitk", 0, DRAG_OPT_PRODUCT)        \
+  X(ATTN_GEN, "attn_gen", 0, DRAG_OPT_PRODUCT)              \
+  X(GEMM_T128, "gemm_t128", 0, DRAG_OPT_PRODUCT)            \
+  X(GEMM_NO_96, "gemm_no_96", 0, DRAG_OPT_PRODUCT)          \
+  X(GEMM_NO_192, "gemm_no_192", 0, DRAG_OPT_PRODUCT)        \
+  X(GEMM_NONPERSISTENT, "gemm_nonpersistent", 0, DRAG_OPT_PRODUCT) \
+  X(GEMM_NARROW, "gemm_narrow", 0, DRAG_OPT_PRODUCT)        \
+  X(CONV_NO_SMALL_COUT, "conv_no_small_cout", 0, DRAG_OPT_PRODUCT) \
+  X(CONV_NO_LIN, "conv_no_lin", 0, DRAG_OPT_PRODUCT)        \
+  X(CONV_TILE, "conv_tile", 0, DRAG_OPT_PRODUCT)
+#define DRAG_OPT_ENUM(id, name, def, exp) DRAG_OPT_##id,
+enum { DRAG_OPTIONS(DRAG_OPT_ENUM) DRAG_OPT_COUNT };
+#undef DRAG_OPT_ENUM
 int drag_opt(int idx);
 // Experiments: code paths whose A/B is recorded and negative (the persistent attention kernel -1 %, the V-one-step-ahead attention
 // schedule 0, several query tiles per top-k workgroup -20 %) are compiled only into a

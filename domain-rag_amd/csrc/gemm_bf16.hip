@@ -1463,14 +1463,11 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_t256_pair(GemmKArgs p) { t25
 // faster one per tile, but it needs enough tiles to fill the 256 CUs and loses to the 128x128 kernel when the last round of
 // tiles is mostly empty (measured at M = 1024 / 1536 / 1753, scripts/bench_gemm_small_m.py: 216 tiles 1226 vs 957 TFLOP/s,
 // 504 tiles 1384 vs 1069, but 72 tiles 510 vs 680 and 288 tiles 927 vs 993).
-// A/B switches are read once per process (not per launch)
-static bool env_flag(const char* name) { return getenv(name) != nullptr; }
 // rows of tiles of height tm over one problem, or over the two row segments of a pair (each segment starts on a tile boundary)
 static long long tile_rows(long long M1, long long M2, int tm) { return (M1 + tm - 1) / tm + (M2 > 0 ? (M2 + tm - 1) / tm : 0); }
 
 static bool use_t256(long long M1, long long M2, int N, int K) {
-  static const bool force_t128 = env_flag("DRAG_GEMM_T128");
-  if (force_t128 || N < 256 || K < 256) return false;
+  if (drag_opt(DRAG_OPT_GEMM_T128) || N < 256 || K < 256) return false;
   const long long M = M1 + M2;
   if (M >= 2048 && M2 == 0) return true;
   if (M < 1024) return false;
@@ -1521,13 +1518,12 @@ static int deep_policy(long long M1, long long M2, int N, int K, long long* cost
   if (tiles128 <= 128) { pick = 24; cost = ((tiles64 + 255) / 256) * (64 + 128); }        // <= 256 workgroups of 64 x 128: one per CU, 4-stage ring (96 KiB)
   else if (tiles128 <= 256) { pick = 23; cost = ((tiles64 + 255) / 256) * (64 + 128); }   // <= 512 workgroups: two per CU, 3-stage ring (72 KiB each)
   else { pick = 0; cost = paired_rounds(tiles128) * (128 + 128); }
-  static const bool no96 = env_flag("DRAG_GEMM_NO_96");
-  if (pick == 0 && !no96) {
+  if (pick == 0 && !drag_opt(DRAG_OPT_GEMM_NO_96)) {
     const long long c96 = paired_rounds(tile_rows(M1, M2, 96) * tn) * (96 + 128);
     if (c96 < cost) { pick = 32; cost = c96; }
   }
   // one round of ring tiles (ties: the larger MI at 128 columns)
-  static const bool no192 = env_flag("DRAG_GEMM_NO_192");
+  const bool no192 = drag_opt(DRAG_OPT_GEMM_NO_192) != 0;
   long long cbest = 0;
   int best = 0;
   if (M >= 256) {
@@ -1545,8 +1541,7 @@ static int deep_policy(long long M1, long long M2, int N, int K, long long* cost
     return best;
   }
   // a partly filled second round of 256x256 tiles
-  static const bool force_t128 = env_flag("DRAG_GEMM_T128");
-  if (pick != 24 && pick != 23 && M >= 1024 && N >= 256 && K >= 256 && !force_t128) {
+  if (pick != 24 && pick != 23 && M >= 1024 && N >= 256 && K >= 256 && !drag_opt(DRAG_OPT_GEMM_T128)) {
     const long long c256 = ((tile_rows(M1, M2, 256) * ((N + 255) / 256) + 255) / 256) * (256 + 256);
     if (c256 < cost) { pick = 2; cost = c256; }
   }
@@ -1564,8 +1559,7 @@ static int t256_grid(int ntiles) {
     ncu = n & ~7;                                  // multiple of the 8 XCDs, so a workgroup's tiles stay on its XCD's L2
     if (ncu == 0) ncu = 8;
   }
-  static const bool nonpersistent = env_flag("DRAG_GEMM_NONPERSISTENT");
-  if (nonpersistent) return ntiles;
+  if (drag_opt(DRAG_OPT_GEMM_NONPERSISTENT)) return ntiles;
   return ntiles < ncu ? ntiles : ncu;
 }
 
@@ -1592,10 +1586,9 @@ static int fill_common(GemmKArgs& k, const void* A, const void* W, void* C, cons
   // it in clock (g = 1 on (42696, 21504, 3072): 23.4 GB and 1.48 GHz; g = 4: 11.5 GB and 1.77 GHz).  4 | 8 are the two minima; the wide
   // launches (N >= 16384: the single blocks' q|k|v|mlp Linear) run 1.5 % faster on 4.
   k.group_m = drag_opt(DRAG_OPT_GEMM_GROUP_M) > 0 ? drag_opt(DRAG_OPT_GEMM_GROUP_M) : (K >= 8192 || N >= 16384 ? 4 : 8);
-  static const bool narrow = env_flag("DRAG_GEMM_NARROW");
   k.wide = !out_f32 && N % 8 == 0 && ldc % 8 == 0 && ((uintptr_t)C & 15) == 0 && (k.cm.rpb >= M || c_bs % 8 == 0) &&
            (!resid || ((uintptr_t)resid & 15) == 0) && (!gate || (((uintptr_t)gate & 15) == 0 && ldg % 8 == 0)) &&
-           !narrow;
+           !drag_opt(DRAG_OPT_GEMM_NARROW);
   k.tiles_m = (M + BM - 1) / BM; k.tiles_n = (N + BN - 1) / BN;
   return k.tiles_m * k.tiles_n;
 }

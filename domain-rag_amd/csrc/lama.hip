@@ -483,9 +483,8 @@ extern "C" int drag_conv2d_f32(const drag_conv2d_f32_args* a, void* stream) {
   ConvK k;
   k.a = *a;
   k.npix = (long long)a->B * a->Ho * a->Wo;
-  static const bool no_small = getenv("DRAG_CONV_NO_SMALL_COUT") != nullptr;
   if (a->Cout <= 4 && a->stride == 1 && !a->transposed && a->KH <= SC_KMAX && a->KW <= SC_KMAX && a->Cin % SC_C == 0 && a->ldx >= a->Cin &&
-      a->B <= 65535 && !no_small) {
+      a->B <= 65535 && !drag_opt(DRAG_OPT_CONV_NO_SMALL_COUT)) {
     dim3 grid((unsigned)((a->Wo + SC_T - 1) / SC_T), (unsigned)((a->Ho + SC_T - 1) / SC_T), (unsigned)a->B);
     if (a->Cout == 1)
       hipLaunchKernelGGL(conv_small_cout_f32_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, k);
@@ -496,15 +495,14 @@ extern "C" int drag_conv2d_f32(const drag_conv2d_f32_args* a, void* stream) {
   }
   // tile policy (speed only — every instantiation produces the same bits): 128x128 tiles when that still launches >= 2
   // workgroups per CU, else 64x64 with 16-channel steps, or 64-channel steps when even those leave CUs with one workgroup
-  static const char* force = getenv("DRAG_CONV_TILE");            // "64x16" | "64x64" | "128" (tests, ablations)
+  const int force = drag_opt(DRAG_OPT_CONV_TILE);                 // 1 = 64x16 | 2 = 64x64 | 3 = 128 (tests, ablations)
   const long long g128 = ((k.npix + 127) / 128) * ((a->Cout + 127) / 128);
   const long long g64 = ((k.npix + 63) / 64) * ((a->Cout + 63) / 64);
   int pick = (a->Cout >= 128 && g128 >= 512) ? 2 : ((a->Cin % 64 == 0 && g64 < 1024) ? 1 : 0);
-  if (force) pick = force[0] == '1' ? 2 : (force[3] == '6' ? 1 : 0);
+  if (force >= 1 && force <= 3) pick = force - 1;
   if (pick == 1 && a->Cin % 64 != 0) pick = 0;
-  static const bool no_lin = getenv("DRAG_CONV_NO_LIN") != nullptr;
   const int tile = pick == 2 ? 128 : 64, step = pick == 1 ? 64 : 16;
-  const bool lin = !no_lin && a->KH == 1 && a->KW == 1 && a->stride == 1 && a->pad == 0 && !a->transposed && a->Hi == a->Ho && a->Wi == a->Wo &&
+  const bool lin = !drag_opt(DRAG_OPT_CONV_NO_LIN) && a->KH == 1 && a->KW == 1 && a->stride == 1 && a->pad == 0 && !a->transposed && a->Hi == a->Ho && a->Wi == a->Wo &&
                    k.npix % tile == 0 && a->Cout % tile == 0 && a->Cin % step == 0;
   if (pick == 2) {
     dim3 grid((unsigned)((k.npix + 127) / 128), (unsigned)((a->Cout + 127) / 128));

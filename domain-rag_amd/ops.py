@@ -6,6 +6,7 @@ here, and nothing falls back to torch when the library is missing (``_lib.load()
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 
@@ -96,8 +97,34 @@ def set_recorder(rec: GemmRecorder | None) -> None:
 
 
 def set_option(name: str, value: int) -> None:
-    """measurement switch of the library (``drag_set_option``): "attn_sched", "attn_w4" """
+    """Set one of the library's measurement switches (``drag_set_option``) for the whole process, from the next launch on.  The comment of
+    ``drag_set_option`` in include/domainrag_hip.h is the list of names, values and defaults (``drag_option_name`` enumerates the names);
+    an unknown name, or a value that only an experiment build carries, raises RuntimeError.  Tests and A/B scripts switch with
+    ``options(...)``, which puts the previous values back."""
     check(_lib.load().drag_set_option(name.encode(), int(value)), "drag_set_option")
+
+
+def get_option(name: str) -> int:
+    """current value of a measurement switch (``drag_get_option``)"""
+    v = ctypes.c_int32()
+    check(_lib.load().drag_get_option(name.encode(), ctypes.byref(v)), "drag_get_option")
+    return v.value
+
+
+@contextlib.contextmanager
+def options(**values: int):
+    """``with ops.options(gemm_kernel=1, gemm_pair=2): ...`` — set switches for the block and put back what they held before it (in reverse
+    order, also when the block raises or a later switch of the list is refused)"""
+    old = []
+    try:
+        for name, v in values.items():
+            prev = get_option(name)
+            set_option(name, v)
+            old.append((name, prev))
+        yield
+    finally:
+        for name, prev in reversed(old):
+            set_option(name, prev)
 
 
 def experiments_built() -> bool:
@@ -188,14 +215,17 @@ def _recorded_attention(call, B, S, H, qprep, vrow):
     if _recorder is None:
         call()
         return
+    # the name before the launch: what the launch is about to read is what gets reported
+    fam = _lib.load().drag_attention_bf16_choice(S, int(vrow), int(qprep))
+    q = "true" if qprep else "false"
+    gen = get_option("attn_gen")
+    variant = f", {gen - 10}" if experiments_built() and 11 <= gen <= 29 else ""     # experiment builds: the generated stream's schedule variants
+    name = {64: f"attention_q64_kernel<{q}>", 640: f"attention_q64g_kernel<{q}, false>", 641: f"attention_q64g_kernel<{q}, true{variant}>"}.get(
+        fam, f"attention_d128_kernel<{fam}, ..., {q}, ...>")
     s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s_ev.record()
     call()
     e_ev.record()
-    fam = _lib.load().drag_attention_bf16_choice(S, int(vrow), int(qprep))
-    q = "true" if qprep else "false"
-    name = {64: f"attention_q64_kernel<{q}>", 640: f"attention_q64g_kernel<{q}, false>", 641: f"attention_q64g_kernel<{q}, true>"}.get(
-        fam, f"attention_d128_kernel<{fam}, ..., {q}, ...>")
     _recorder.attn.append((s_ev, e_ev, 4.0 * S * S * 128 * H * B, name))
 
 

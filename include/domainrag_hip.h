@@ -24,23 +24,54 @@ extern "C" {
 
 int drag_version(void);
 const char* drag_last_error(void);
-/* Measurement switches (A/B of kernel variants inside one process; every setting computes the same function):
- *   "attn_sched" 0 | 1 | 2 (schedule of the attention kernel's KV-tile loop), "attn_w4" 0 | 1 (128-query blocks at any
- *   length), "attn_tune" bit 0: static wave priority, bit 1: 16-byte epilogue stores, "attn_q64" 0 | 1 | 2 (the 4-wave x 64-query
- *   kernel: by policy — joint sequences of 4096 keys and more that fill the chip | whenever S >= 1024 | never), "attn_persist" 0 | 1 | n >= 3 (persistent attention experiment: off, one workgroup per
- *   CU, n per XCD), "gemm_kernel", "gemm_group_m", "ln_generic", "topk_grid" (workgroups at most of the top-k scan, 0 = 512),
- *   "topk_depth" 0 | 3 (LDS-DMA ring depth of the scan), "topk_qt" 0 | 2 | 4 (query tiles per scan workgroup), "topk_select" 0 | 256 | 1024,
- *   "topk_dense_sample" 0 | 1 (threshold from every sampled row instead of the group maxima), "topk_path" 0 | 1 | 2 (top-k call: two launches
- *   through the row groups' maxima by policy — k <= 128 and 8 192 < N <= 131 072, or N <= 524 288 with at most 4 queries | always the
- *   sampled-threshold form | the two-launch form wherever it applies: k <= 128, 8 192 < N <= 1 048 576), "gemm_pair" 0 | 1 | 2
- *   (drag_gemm_bf16_pair: merge unless both problems fill the chip alone | never | always), "topk_qreg" 0 | 1 (d = 512 scan: query tile in
- *   registers | read from LDS per corpus chunk), "gemm_w4" 0 | 1 | 2 | 3 (gemm_bf16_w4p by policy | never | wherever it can run | launches of
- *   >= 256 tiles), "attn_walk" 0 | 2 | n (the 64-query attention kernel: one workgroup per CU walks the (batch-head, query block) items when
- *   it can | one item per workgroup | n workgroups, n a multiple of 8), "gemm_splitk" 0 | 1 | n (split-K by policy | never | n slices wherever valid: see
- *   drag_gemm_set_workspace).
- * Initial values: $DRAG_ATTN_SCHED, $DRAG_ATTN_W4, $DRAG_ATTN_TUNE, $DRAG_ATTN_Q64, $DRAG_ATTN_PERSIST, $DRAG_GEMM_KERNEL,
- * $DRAG_GEMM_GROUP_M, $DRAG_LN_GENERIC, $DRAG_TOPK_GRID, $DRAG_TOPK_DEPTH, $DRAG_TOPK_QT, $DRAG_TOPK_SELECT, $DRAG_TOPK_DENSE_SAMPLE, $DRAG_TOPK_PATH, $DRAG_GEMM_PAIR, $DRAG_TOPK_QREG, $DRAG_GEMM_W4, $DRAG_ATTN_WALK, $DRAG_GEMM_SPLITK.  Returns 0, or -1 for an unknown name. */
+/* Measurement switches (A/B of kernel variants inside one process; every setting computes the same function, and the same bits unless
+ * its line says otherwise).  The list below is the list: one line per switch, the default first.
+ *   "attn_sched"          2 | 0 | 1 | 3   schedule of the attention kernel's KV-tile loop (3: experiment builds only)
+ *   "attn_w4"             0 | 1           128-query attention blocks at any length
+ *   "attn_tune"           2 | bits        bit 0: static wave priority, bit 1: 16-byte epilogue stores
+ *   "attn_q64"            0 | 1 | 2       the 4-wave x 64-query attention kernel: by policy (joint sequences of 4096 keys and more that fill
+ *                                         the chip) | whenever S >= 1024 | never
+ *   "attn_persist"        0 | 1 | n >= 3  persistent attention (experiment builds only): off | one workgroup per CU | n per XCD
+ *   "attn_walk"           0 | 2 | n       the 64-query attention kernel: one workgroup per CU walks the (batch-head, query block) items when it
+ *                                         can | one item per workgroup | n workgroups, n a multiple of 8
+ *   "attn_gen"            0 | 1 | 2       the 64-query kernel's KV loop as one generated instruction stream: whenever the KV tiles pair up, with
+ *                                         the scale folded into the fused q preparation (its own, equally accurate rounding) | the hand-placed
+ *                                         kernel | the generated stream without the fold (the hand-placed kernel's bits); 11..29 select
+ *                                         schedule variants in experiment builds
+ *   "gemm_kernel"         0 | code        tile policy | 1 = 128x128, 2 = 256x256 (8 waves), 3 = 256x256 (4 waves), from 10 on the ring kernels'
+ *                                         codes as drag_gemm_bf16_choice reports them (400 / 401: experiment builds only)
+ *   "gemm_t128"           0 | 1           withdraw the 256x256 kernels from the tile policy and leave the rest to it (not "gemm_kernel" = 1)
+ *   "gemm_no_96"          0 | 1           withdraw the 96-row tiles from the tile policy
+ *   "gemm_no_192"         0 | 1           withdraw the 192-column tiles from the tile policy
+ *   "gemm_nonpersistent"  0 | 1           the 256x256 kernel: one workgroup per tile instead of one per CU
+ *   "gemm_narrow"         0 | 1           the fragment-layout epilogue where the staged 16-byte one would apply
+ *   "gemm_epilogue"       0 | 1 | 2       1 = the general epilogue for every tile, 2 = the 4-wave kernel prepares the tile after next's state
+ *                                         in front of the epilogue (experiment builds only; ignored otherwise)
+ *   "gemm_group_m"        0 | n           M tiles per group of the tile walk (0 = 4 or 8 by shape)
+ *   "gemm_pair"           0 | 1 | 2       drag_gemm_bf16_pair: merge unless both problems fill the chip alone | never | always
+ *   "gemm_w4"             0 | 1 | 2 | 3   gemm_bf16_w4p by policy | never | wherever it can run | launches of >= 256 tiles
+ *   "gemm_splitk"         0 | 1 | n       split-K by policy | never | n slices wherever valid (see drag_gemm_set_workspace); a split launch sums
+ *                                         its slices' f32 chains: the last bit may differ
+ *   "ln_generic"          0 | 1           the any-width LayerNorm kernel where the fixed-width (3072) one would apply
+ *   "conv_no_small_cout"  0 | 1           drag_conv2d_f32 without its kernel for <= 4 output channels
+ *   "conv_no_lin"         0 | 1           drag_conv2d_f32: the general form (per-load predicates) for 1x1 convolutions too
+ *   "conv_tile"           0 | 1 | 2 | 3   drag_conv2d_f32 tiles by policy | 64x64, 16-channel steps | 64x64, 64-channel steps | 128x128
+ *   "topk_grid"           0 | n           workgroups at most of the top-k scan (0 = 512)
+ *   "topk_depth"          0 | 3           LDS-DMA ring depth of the scan
+ *   "topk_qt"             0 | 2 | 4       query tiles per scan workgroup (experiment builds only)
+ *   "topk_qreg"           0 | 1           d = 512 scan: query tile in registers | read from LDS per corpus chunk
+ *   "topk_select"         0 | 256 | 1024  threads of a selection workgroup (0 = 1024)
+ *   "topk_dense_sample"   0 | 1           threshold from every sampled row instead of the group maxima
+ *   "topk_path"           0 | 1 | 2       top-k call: two launches through the row groups' maxima by policy (k <= 128 and 8 192 < N <= 131 072,
+ *                                         or N <= 524 288 with at most 4 queries) | always the sampled-threshold form | the two-launch form
+ *                                         wherever it applies (k <= 128, 8 192 < N <= 1 048 576)
+ * Initial value of each: the environment variable DRAG_ + the name in upper case ($DRAG_ATTN_SCHED, ...), read once when the library first
+ * needs a switch: unset = the default, set but empty = 1, else the number.  drag_set_option returns 0, or -1 for an unknown name or a value
+ * that needs an experiment build; drag_get_option reads a switch back (0, or -1 for an unknown name); drag_option_name(i) enumerates the
+ * names, NULL past the end. */
 int drag_set_option(const char* name, int32_t value);
+int drag_get_option(const char* name, int32_t* value);
+const char* drag_option_name(int32_t index);
 /* 1 when the library was built with DRAG_EXPERIMENTS=1 and carries the kernels behind "attn_persist", "attn_sched" = 3 and "topk_qt"
  * (measured non-improvements kept for their A/B records), else 0.  A pure query: no option is touched. */
 int drag_experiments_built(void);

@@ -28,13 +28,10 @@ for (B, S, H) in [(1, 5337, 24), (8, 5337, 24), (8, 1753, 24), (8, 729, 16)]:
     t = {k: [] for k in VARIANTS}
     t["row-major v"] = []
     for rep in range(6):
-        for name, env in VARIANTS.items():
-            for k in ("attn_sched", "attn_w4", "attn_tune", "attn_q64"): ops.set_option(k, 0)
-            for k, v in env.items(): ops.set_option(k, v)
-            if rep == 0: bench(run, 3)
-            t[name].append(bench(run))
-        ops.set_option("attn_sched", 2); ops.set_option("attn_w4", 0); ops.set_option("attn_tune", 2); ops.set_option("attn_q64", 0)
-        if rep == 0: bench(run_v, 3)
+        for name, opts in VARIANTS.items():
+            with ops.options(**{"attn_sched": 0, "attn_w4": 0, "attn_tune": 0, "attn_q64": 0, **opts}):
+                if rep == 0: bench(run, 3)
+                t[name].append(bench(run))
+        if rep == 0: bench(run_v, 3)            # (under the library's defaults)
         t["row-major v"].append(bench(run_v))
-    ops.set_option("attn_sched", 2); ops.set_option("attn_w4", 0); ops.set_option("attn_tune", 2); ops.set_option("attn_q64", 0)
     print(f"attn B={B} S={S} H={H}: " + " | ".join(f"{k} {fl/statistics.median(v)/1e9:.0f} TF/s" for k, v in t.items()), flush=True)

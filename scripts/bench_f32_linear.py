@@ -1,5 +1,5 @@
 """float32 matrix-core Linears of the CLIP ViT-B/32 tower (conv2d_f32_kernel as a 1x1 convolution) at batch 1024 / 256 / 100 tokens-rows:
-TFLOP/s per shape.  DRAG_CONV_NO_LIN=1 takes the general convolution form (per-load predicates) for an A/B."""
+TFLOP/s per shape.  The option "conv_no_lin" (DRAG_CONV_NO_LIN=1, or ops.options(conv_no_lin=1)) takes the general convolution form (per-load predicates) for an A/B."""
 import os, sys, statistics
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -206,11 +206,8 @@ def test_gemm_pair_and_two_destinations_with_outliers(gpu):
     a1, w1, _ = _outlier_operands(1024, N, K, 31, 1e3)
     a2, w2, _ = _outlier_operands(512, N, K, 32, 1e2)
     o1 = torch.empty(1024, N, dtype=torch.bfloat16, device=gpu); o2 = torch.empty(512, N, dtype=torch.bfloat16, device=gpu)
-    ops.set_option("gemm_pair", 2)
-    try:
+    with ops.options(gemm_pair=2):
         ops.gemm_pair(dict(a=a1.to(gpu), w=w1.to(gpu), out=o1), dict(a=a2.to(gpu), w=w2.to(gpu), out=o2))
-    finally:
-        ops.set_option("gemm_pair", 0)
     _gemm_check(o1, a1, w1, what="pair, first segment")
     _gemm_check(o2, a2, w2, what="pair, second segment")
     a3, w3, _ = _outlier_operands(2500, 1024, 1024, 33, 1e3)
@@ -224,14 +221,9 @@ def test_gemm_pair_and_two_destinations_with_outliers(gpu):
 # kernel (>= 768 tiles, or >= 256 with K >= 8192), whose evidence was bit-equality with the 8-wave kernel on N(0, 1) operands.  Here it is
 # checked against float64 directly: FORCED ("gemm_kernel" = 3) on shapes small enough for a host float64 product, and through the POLICY on
 # shapes it really takes (the float64 product then on the GPU, by torch — the checker, not the product).
-class _forced_w4p:
-    def __enter__(self):
-        from domain_rag_amd import ops
-        ops.set_option("gemm_kernel", 3)
-
-    def __exit__(self, *exc):
-        from domain_rag_amd import ops
-        ops.set_option("gemm_kernel", 0)
+def _forced_w4p():
+    from domain_rag_amd import ops
+    return ops.options(gemm_kernel=3)
 
 
 def _gemm_check_gpu(out, a, w, *, bias=None, what="", extra_roundings=0):
@@ -579,12 +571,9 @@ def test_attention_on_outlier_channels_and_near_duplicate_keys(gpu, S):
     ref = ops_ref.attention_ref_f64(q, k, v, scale)
     outs = []
     for q64 in (2, 1):                                          # 8-wave family, 64-query kernel
-        ops.set_option("attn_q64", q64)
-        try:
+        with ops.options(attn_q64=q64):
             o = torch.full((B, S, D), float("nan"), dtype=torch.bfloat16, device=gpu)
             ops.attention(qd, qd.view(-1)[D:], vt, o, B, S, H, 3 * D, S * 3 * D, D, S * D, scale)
-        finally:
-            ops.set_option("attn_q64", 0)
         o = o.cpu()
         assert torch.isfinite(o.float()).all()
         # P is rounded to bf16 before P V (like every flash kernel): 2^-8 of the value range per row + the output rounding

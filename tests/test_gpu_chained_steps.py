@@ -145,15 +145,12 @@ def test_fill_chained_steps_through_the_folded_64_query_attention(gpu):
     (1024 image + 100 text tokens = 18 KV tiles, the last one ragged), "attn_q64" = 1 (the policy takes the 64-query kernel from 4096 keys on),
     6 Fill steps over 2 double + 4 single blocks at the real width, the same per-step bars as the 30-step run"""
     from domain_rag_amd import _lib, ops
-    try:
-        ops.set_option("attn_q64", 1)
+    with ops.options(attn_q64=1):
         assert _lib.load().drag_attention_bf16_choice(1024 + 100, 0, 1) == 641
         _fill_chain(gpu, "fill6_q64_fold", "Fill, 6 steps, strength 1.0, 512x512 (S = 1124), 2 double + 4 single blocks at D=3072, attention_q64g_kernel<true, true>",
                     512, 6, 100, 2, 4, 40, (180, 332, 160, 340), pixel_max_ratio=RATIO, pixel_mean_ratio=RATIO_RMS)
         # (pixels: the MAXIMUM over 786 432 values of one realisation moves by 15 % with the oracle's own summation order — 0.0203 with 64 host
         #  threads, 0.0177 with 32, HIP 0.0236 both times — so it gets this file's max-norm ratio, 1.4, and the MEAN the tight one, 1.1)
-    finally:
-        ops.set_option("attn_q64", 0)
 
 
 def test_txt2img_50_chained_steps_vs_oracle_per_step(gpu):

@@ -243,30 +243,28 @@ def test_configs1_shape_routes_are_bit_identical_and_match_oracle(gpu, monkeypat
     #  into a pair — sums S f32 chains instead of one: the one kernel choice that moves the last bit.  The bit comparisons between routes
     #  and batch sizes run with it off; the split route is held to the oracle's bar below)
     split = run(1)
-    ops.set_option("gemm_splitk", 1)
-    merged = run(1)
-    try:
-        ops.set_option("gemm_pair", 1)
-        monkeypatch.setattr(flux_mod, "_FUSED_QKV_MLP", False)
-        plain = run(1)
-        monkeypatch.setattr(flux_mod, "_FUSED_QKV_MLP", True)
-        ops.set_option("gemm_pair", 2)
-        forced = run(1)
-    finally:
-        ops.set_option("gemm_pair", 0)
-        monkeypatch.setattr(flux_mod, "_FUSED_QKV_MLP", None)
-    assert torch.equal(merged, plain), "merged / fused route differs from one launch per Linear"
-    assert torch.equal(forced, plain), "always-merged, always-fused route differs"
-    out4 = run(B)
-    for i in range(B):
-        one = model(hidden[i:i + 1].to(gpu), enc[i:i + 1].to(gpu), pooled[i:i + 1].to(gpu), t[:1], img_ids, txt_ids, None)
-        assert torch.equal(one[0], out4[i]), f"image {i}: batch row differs from the single-image run"
+    with ops.options(gemm_splitk=1):
+        merged = run(1)
+        try:
+            monkeypatch.setattr(flux_mod, "_FUSED_QKV_MLP", False)
+            with ops.options(gemm_pair=1):
+                plain = run(1)
+            monkeypatch.setattr(flux_mod, "_FUSED_QKV_MLP", True)
+            with ops.options(gemm_pair=2):
+                forced = run(1)
+        finally:
+            monkeypatch.setattr(flux_mod, "_FUSED_QKV_MLP", None)
+        assert torch.equal(merged, plain), "merged / fused route differs from one launch per Linear"
+        assert torch.equal(forced, plain), "always-merged, always-fused route differs"
+        out4 = run(B)
+        for i in range(B):
+            one = model(hidden[i:i + 1].to(gpu), enc[i:i + 1].to(gpu), pooled[i:i + 1].to(gpu), t[:1], img_ids, txt_ids, None)
+            assert torch.equal(one[0], out4[i]), f"image {i}: batch row differs from the single-image run"
     ocfg = oflux.FluxConfig(**{k: getattr(cfg, k) for k in cfg.__dataclass_fields__})
     with torch.no_grad():
         ref = oflux.flux_forward(params, ocfg, hidden[:1], enc[:1], pooled[:1], t[:1], img_ids, txt_ids, None)
         ref32 = oflux.flux_forward({k: v.float() for k, v in params.items()}, ocfg, hidden[:1].float(), enc[:1].float(), pooled[:1].float(),
                                    t[:1], img_ids, txt_ids, None, time_dtype=torch.bfloat16)
-    ops.set_option("gemm_splitk", 0)
     e, e_or = _rel(merged, ref32), _rel(ref, ref32)
     assert e < _tol(e_or, 1e-2), _msg("configs[1] shape", e, e_or)
     e_s = _rel(split, ref32)

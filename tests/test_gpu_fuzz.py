@@ -85,45 +85,42 @@ def test_attention_q64_equals_the_8_wave_kernel_on_ragged_shapes(gpu):
     rng = np.random.default_rng(11)
     g = torch.Generator().manual_seed(5)
     cases = [(1, 1024, 1), (1, 1025, 3), (2, 1087, 5), (1, 1100, 2), (3, 4096, 2), (1, 4097, 9), (1, 5337, 3), (2, 2111, 8), (1, 8191, 1)]
-    try:
-        for ci, (B, S, H) in enumerate(cases):
-            D = H * 128
-            scale_in = float(rng.choice([0.5, 1.0, 6.0])) if ci >= 3 else (0.5, 1.0, 6.0)[ci]
-            qkv = (torch.randn(B, S, 3 * D, generator=g) * scale_in).bfloat16().to(gpu)
-            s_txt = int(rng.integers(0, min(S, 600)))
-            w = [(1 + 0.1 * torch.randn(128, generator=g)).bfloat16().to(gpu) for _ in range(4)]
-            ang = torch.rand(S, 64, generator=g) * 6.28
-            cos, sin = torch.cos(ang).contiguous().to(gpu), torch.sin(ang).contiguous().to(gpu)
-            vt = torch.empty(B, H, 128, (S + 63) // 64 * 64, device=gpu, dtype=torch.bfloat16)
-            # two-pass route: q, k prepared in place
-            q2 = qkv.clone()
-            ops.qk_norm_rope_vt(q2, vt, None, None, None, None, None, None, B, S, H, 3 * D, 0)
-            outs = {}
-            for q64 in (2, 1, 3):           # 3: the generated stream (no fold without the fused q preparation)
-                ops.set_option("attn_q64", 2 if q64 == 2 else 1); ops.set_option("attn_gen", 2 if q64 == 3 else 1)
+    for ci, (B, S, H) in enumerate(cases):
+        D = H * 128
+        scale_in = float(rng.choice([0.5, 1.0, 6.0])) if ci >= 3 else (0.5, 1.0, 6.0)[ci]
+        qkv = (torch.randn(B, S, 3 * D, generator=g) * scale_in).bfloat16().to(gpu)
+        s_txt = int(rng.integers(0, min(S, 600)))
+        w = [(1 + 0.1 * torch.randn(128, generator=g)).bfloat16().to(gpu) for _ in range(4)]
+        ang = torch.rand(S, 64, generator=g) * 6.28
+        cos, sin = torch.cos(ang).contiguous().to(gpu), torch.sin(ang).contiguous().to(gpu)
+        vt = torch.empty(B, H, 128, (S + 63) // 64 * 64, device=gpu, dtype=torch.bfloat16)
+        # two-pass route: q, k prepared in place
+        q2 = qkv.clone()
+        ops.qk_norm_rope_vt(q2, vt, None, None, None, None, None, None, B, S, H, 3 * D, 0)
+        outs = {}
+        for q64 in (2, 1, 3):           # 3: the generated stream (no fold without the fused q preparation)
+            with ops.options(attn_q64=2 if q64 == 2 else 1, attn_gen=2 if q64 == 3 else 1):
                 o = torch.full((B, S, D), float("nan"), device=gpu, dtype=torch.bfloat16)
                 ops.attention(q2, q2.view(-1)[D:], vt, o, B, S, H, 3 * D, S * 3 * D, D, S * D, 1 / math.sqrt(128))
-                outs[q64] = o.cpu()
-            assert torch.isfinite(outs[2].float()).all(), (B, S, H)
-            assert torch.equal(outs[1], outs[2]) and torch.equal(outs[3], outs[2]), ("two-pass", B, S, H, scale_in)
-            if ci < 3:
-                q, k, v = (qkv.cpu()[..., i * D:(i + 1) * D].view(B, S, H, 128).transpose(1, 2).float() for i in range(3))
-                assert _rel(outs[1], ops_ref.attention_ref(q, k, v, 1 / math.sqrt(128))) < 1.5e-2, (B, S, H, scale_in)
-            # fused route: k / v prepared by the pass, q inside the attention kernel
-            q3 = qkv.clone()
-            ops.k_norm_rope_vt(q3, vt, w[1], w[3], cos, sin, B, S, H, 3 * D, s_txt)
-            # 2: the 8-wave kernel; 1: the hand-placed 64-query kernel; 3: round 6's generated stream without the fold (even tile counts; the
-            # hand-placed kernel elsewhere); 4: with the fold — the product's choice, its own evaluation: held to the 8-wave kernel's neighbourhood
-            for q64 in (2, 1, 3, 4):
-                ops.set_option("attn_q64", 2 if q64 == 2 else 1); ops.set_option("attn_gen", {2: 1, 1: 1, 3: 2, 4: 0}[q64])
+            outs[q64] = o.cpu()
+        assert torch.isfinite(outs[2].float()).all(), (B, S, H)
+        assert torch.equal(outs[1], outs[2]) and torch.equal(outs[3], outs[2]), ("two-pass", B, S, H, scale_in)
+        if ci < 3:
+            q, k, v = (qkv.cpu()[..., i * D:(i + 1) * D].view(B, S, H, 128).transpose(1, 2).float() for i in range(3))
+            assert _rel(outs[1], ops_ref.attention_ref(q, k, v, 1 / math.sqrt(128))) < 1.5e-2, (B, S, H, scale_in)
+        # fused route: k / v prepared by the pass, q inside the attention kernel
+        q3 = qkv.clone()
+        ops.k_norm_rope_vt(q3, vt, w[1], w[3], cos, sin, B, S, H, 3 * D, s_txt)
+        # 2: the 8-wave kernel; 1: the hand-placed 64-query kernel; 3: round 6's generated stream without the fold (even tile counts; the
+        # hand-placed kernel elsewhere); 4: with the fold — the product's choice, its own evaluation: held to the 8-wave kernel's neighbourhood
+        for q64 in (2, 1, 3, 4):
+            with ops.options(attn_q64=2 if q64 == 2 else 1, attn_gen={2: 1, 1: 1, 3: 2, 4: 0}[q64]):
                 o = torch.full((B, S, D), float("nan"), device=gpu, dtype=torch.bfloat16)
                 ops.attention_qprep(q3, q3.view(-1)[D:], vt, o, B, S, H, 3 * D, S * 3 * D, D, S * D, 1 / math.sqrt(128), w[0], w[2], cos, sin, s_txt)
-                outs[q64] = o.cpu()
-            assert all(torch.isfinite(outs[q].float()).all() for q in (1, 2, 3, 4)), (B, S, H)
-            assert torch.equal(outs[1], outs[2]) and torch.equal(outs[3], outs[2]), ("fused q preparation", B, S, H, scale_in, s_txt)
-            assert _rel(outs[4], outs[2]) < 1e-2, ("fused q preparation, fold", B, S, H, scale_in, _rel(outs[4], outs[2]))
-    finally:
-        ops.set_option("attn_q64", 0); ops.set_option("attn_gen", 0)
+            outs[q64] = o.cpu()
+        assert all(torch.isfinite(outs[q].float()).all() for q in (1, 2, 3, 4)), (B, S, H)
+        assert torch.equal(outs[1], outs[2]) and torch.equal(outs[3], outs[2]), ("fused q preparation", B, S, H, scale_in, s_txt)
+        assert _rel(outs[4], outs[2]) < 1e-2, ("fused q preparation, fold", B, S, H, scale_in, _rel(outs[4], outs[2]))
 
 
 def test_resample_random_sizes(gpu):
@@ -252,31 +249,26 @@ def test_topk_fuzz_with_ties_nonfinite_rows_and_every_measurement_option(gpu):
     from oracle import retrieval as oret
     rng = np.random.default_rng(2024)
     names = ("topk_qt", "topk_grid", "topk_depth", "topk_dense_sample", "topk_select")
-    try:
-        for c in range(28):
-            d = int(rng.choice([64, 128, 512]))
-            N = int(rng.choice([rng.integers(1, 600), rng.integers(600, 9000), rng.integers(8193, 50000)]))
-            Q = int(rng.choice([1, rng.integers(1, 17), rng.integers(17, 65), rng.integers(65, 140)]))
-            k = int(rng.choice([1, rng.integers(1, 129), rng.integers(129, 2049)]))
-            pool = rng.standard_normal((max(1, int(N * rng.choice([1.0, 0.3, 0.02]))), d)).astype(np.float32)
-            corpus = pool[rng.integers(0, len(pool), N)]
-            if rng.random() < 0.3 and N > 10:
-                corpus[rng.integers(0, N)] = np.nan; corpus[rng.integers(0, N)] = np.inf; corpus[rng.integers(0, N), 0] = -np.inf
-            q = rng.standard_normal((Q, d)).astype(np.float32)
-            opts = dict(zip(names, (int(rng.choice([0, 2, 4])), int(rng.choice([0, 16, 256, 1024, 2048])), int(rng.choice([0, 3])),
-                                    int(rng.integers(0, 2)), int(rng.choice([0, 256, 1024])))))
-            if not ops.experiments_built():
-                opts["topk_qt"] = 0                 # several query tiles per workgroup: DRAG_EXPERIMENTS builds only
-            opts["topk_path"] = c % 2               # odd cases: the sampled-threshold form even where the two-launch form applies
-            for n_, v in opts.items():
-                ops.set_option(n_, v)
+    for c in range(28):
+        d = int(rng.choice([64, 128, 512]))
+        N = int(rng.choice([rng.integers(1, 600), rng.integers(600, 9000), rng.integers(8193, 50000)]))
+        Q = int(rng.choice([1, rng.integers(1, 17), rng.integers(17, 65), rng.integers(65, 140)]))
+        k = int(rng.choice([1, rng.integers(1, 129), rng.integers(129, 2049)]))
+        pool = rng.standard_normal((max(1, int(N * rng.choice([1.0, 0.3, 0.02]))), d)).astype(np.float32)
+        corpus = pool[rng.integers(0, len(pool), N)]
+        if rng.random() < 0.3 and N > 10:
+            corpus[rng.integers(0, N)] = np.nan; corpus[rng.integers(0, N)] = np.inf; corpus[rng.integers(0, N), 0] = -np.inf
+        q = rng.standard_normal((Q, d)).astype(np.float32)
+        opts = dict(zip(names, (int(rng.choice([0, 2, 4])), int(rng.choice([0, 16, 256, 1024, 2048])), int(rng.choice([0, 3])),
+                                int(rng.integers(0, 2)), int(rng.choice([0, 256, 1024])))))
+        if not ops.experiments_built():
+            opts["topk_qt"] = 0                 # several query tiles per workgroup: DRAG_EXPERIMENTS builds only
+        opts["topk_path"] = c % 2               # odd cases: the sampled-threshold form even where the two-launch form applies
+        with ops.options(**opts):
             D, I = ops.cosine_topk(torch.from_numpy(corpus).to(gpu), torch.from_numpy(q).to(gpu), k)
-            Dr, Ir = oret.cosine_topk(corpus, q, k)
-            assert np.array_equal(I.cpu().numpy(), Ir), (c, N, d, Q, k, opts)
-            assert np.array_equal(D.cpu().numpy().view(np.uint32), Dr.view(np.uint32)), (c, N, d, Q, k, opts)
-    finally:
-        for n_ in names + ("topk_path",):
-            ops.set_option(n_, 0)
+        Dr, Ir = oret.cosine_topk(corpus, q, k)
+        assert np.array_equal(I.cpu().numpy(), Ir), (c, N, d, Q, k, opts)
+        assert np.array_equal(D.cpu().numpy().view(np.uint32), Dr.view(np.uint32)), (c, N, d, Q, k, opts)
 
 
 def test_topk_adversarial_score_layouts(gpu):
@@ -309,14 +301,11 @@ def test_topk_adversarial_score_layouts(gpu):
         for Q in (1, 16, 64):
             q = (u[None, :] * (1 + np.arange(Q)[:, None] / 8) + 0.01 * rng.standard_normal((Q, d))).astype(np.float32)
             Dr, Ir = oret.cosine_topk(corpus, q, k)
-            try:
-                for path in (0, 1):                  # two launches through the group maxima | sampled threshold + filtered scan
-                    ops.set_option("topk_path", path)
+            for path in (0, 1):                  # two launches through the group maxima | sampled threshold + filtered scan
+                with ops.options(topk_path=path):
                     D, I = ops.cosine_topk(torch.from_numpy(corpus).to(gpu), torch.from_numpy(q).to(gpu), k)
                     assert np.array_equal(I.cpu().numpy(), Ir), (name, Q, path)
                     assert np.array_equal(D.cpu().numpy().view(np.uint32), Dr.view(np.uint32)), (name, Q, path)
-            finally:
-                ops.set_option("topk_path", 0)
 
 
 def test_gemm_pair_random_configs(gpu):
@@ -327,56 +316,53 @@ def test_gemm_pair_random_configs(gpu):
     rng = np.random.default_rng(4321)
     g = torch.Generator().manual_seed(77)
     codes = [0, 0, 1, 2, 14, 24, 23, 32, 33, 43, 113, 123, 133, 143]
-    try:
-        for case in range(36):
-            K = int(rng.choice([64, 128, 256, 320, 512, 1024]))
-            N = int(rng.choice([8, 72, 192, 256, 264, 384, 576, 768, 1032, 1536]))
-            M = [int(rng.choice([1, 7, 33, 77, 128, 255, 300, 512, 777, 1024, 1241, 2100])) for _ in range(2)]
-            Bt = [int(rng.choice([1, 1, 2, 3])) for _ in range(2)]              # batches per segment (rows per batch = M / B when it divides)
-            act = int(rng.choice([0, 0, 1, 2, 3]))
-            mode = str(rng.choice(["plain", "resid", "gate", "f32"]))
-            use_bias = bool(rng.random() < 0.7)
-            code = int(rng.choice(codes))
-            if code >= 100 and N % 192:
-                code = 0
-            segs = []
-            for sgi in range(2):
-                rows = M[sgi]
-                B = Bt[sgi] if rows % Bt[sgi] == 0 else 1
-                rpb, pad = rows // B, int(rng.integers(0, 9)) * 8
-                a = torch.randn(B, rpb + pad, K, generator=g).bfloat16().to(gpu)
-                w = (torch.randn(N, K, generator=g) * 0.05).bfloat16().to(gpu)
-                bias = torch.randn(N, generator=g).bfloat16().to(gpu) if use_bias else None
-                x = torch.randn(B, rpb + pad, N + 8, generator=g).to(torch.float32 if mode == "f32" else torch.bfloat16).to(gpu)
-                gate = torch.randn(B, N + 16, generator=g).bfloat16().to(gpu) if mode == "gate" else None
-                kw = dict(a=a, w=w, bias=bias, M=rows, lda=K, a_rows_per_batch=rpb, a_batch_stride=(rpb + pad) * K,
-                          ldc=N + 8, c_rows_per_batch=rpb, c_batch_stride=(rpb + pad) * (N + 8), act=act, act_n0=(N // 8) * 4)
-                if mode == "f32":
-                    kw["out_f32"] = True
-                if mode in ("resid", "gate"):
-                    kw["resid"] = "self"
-                if mode == "gate":
-                    kw.update(gate=gate, ldg=N + 16)
-                segs.append((kw, x))
+    for case in range(36):
+        K = int(rng.choice([64, 128, 256, 320, 512, 1024]))
+        N = int(rng.choice([8, 72, 192, 256, 264, 384, 576, 768, 1032, 1536]))
+        M = [int(rng.choice([1, 7, 33, 77, 128, 255, 300, 512, 777, 1024, 1241, 2100])) for _ in range(2)]
+        Bt = [int(rng.choice([1, 1, 2, 3])) for _ in range(2)]              # batches per segment (rows per batch = M / B when it divides)
+        act = int(rng.choice([0, 0, 1, 2, 3]))
+        mode = str(rng.choice(["plain", "resid", "gate", "f32"]))
+        use_bias = bool(rng.random() < 0.7)
+        code = int(rng.choice(codes))
+        if code >= 100 and N % 192:
+            code = 0
+        segs = []
+        for sgi in range(2):
+            rows = M[sgi]
+            B = Bt[sgi] if rows % Bt[sgi] == 0 else 1
+            rpb, pad = rows // B, int(rng.integers(0, 9)) * 8
+            a = torch.randn(B, rpb + pad, K, generator=g).bfloat16().to(gpu)
+            w = (torch.randn(N, K, generator=g) * 0.05).bfloat16().to(gpu)
+            bias = torch.randn(N, generator=g).bfloat16().to(gpu) if use_bias else None
+            x = torch.randn(B, rpb + pad, N + 8, generator=g).to(torch.float32 if mode == "f32" else torch.bfloat16).to(gpu)
+            gate = torch.randn(B, N + 16, generator=g).bfloat16().to(gpu) if mode == "gate" else None
+            kw = dict(a=a, w=w, bias=bias, M=rows, lda=K, a_rows_per_batch=rpb, a_batch_stride=(rpb + pad) * K,
+                      ldc=N + 8, c_rows_per_batch=rpb, c_batch_stride=(rpb + pad) * (N + 8), act=act, act_n0=(N // 8) * 4)
+            if mode == "f32":
+                kw["out_f32"] = True
+            if mode in ("resid", "gate"):
+                kw["resid"] = "self"
+            if mode == "gate":
+                kw.update(gate=gate, ldg=N + 16)
+            segs.append((kw, x))
 
-            def call(fn):
-                outs, kws = [], []
-                for kw, x in segs:
-                    o = x.clone()
-                    k2 = dict(kw, out=o)
-                    if k2.get("resid") == "self":
-                        k2["resid"] = o
-                    outs.append(o); kws.append(k2)
-                fn(kws)
-                return [o.cpu() for o in outs]
-            ops.set_option("gemm_kernel", 0); ops.set_option("gemm_pair", 1)
+        def call(fn):
+            outs, kws = [], []
+            for kw, x in segs:
+                o = x.clone()
+                k2 = dict(kw, out=o)
+                if k2.get("resid") == "self":
+                    k2["resid"] = o
+                outs.append(o); kws.append(k2)
+            fn(kws)
+            return [o.cpu() for o in outs]
+        with ops.options(gemm_kernel=0, gemm_pair=1):
             ref = call(lambda kws: [ops.gemm(**{k: v for k, v in kw.items()}) for kw in kws])
-            ops.set_option("gemm_kernel", code); ops.set_option("gemm_pair", 2 if code or rng.random() < 0.5 else 0)
+        with ops.options(gemm_kernel=code, gemm_pair=2 if code or rng.random() < 0.5 else 0):
             got = call(lambda kws: ops.gemm_pair(kws[0], kws[1]))
-            for sgi in range(2):
-                assert torch.equal(ref[sgi], got[sgi]), (case, sgi, M, N, K, code, mode, act)
-                x0 = segs[sgi][1].cpu()
-                rpb = segs[sgi][0]["a_rows_per_batch"]
-                assert torch.equal(got[sgi][:, rpb:], x0[:, rpb:]) and torch.equal(got[sgi][:, :, N:], x0[:, :, N:]), (case, "wrote outside its rows / columns")
-    finally:
-        ops.set_option("gemm_kernel", 0); ops.set_option("gemm_pair", 0)
+        for sgi in range(2):
+            assert torch.equal(ref[sgi], got[sgi]), (case, sgi, M, N, K, code, mode, act)
+            x0 = segs[sgi][1].cpu()
+            rpb = segs[sgi][0]["a_rows_per_batch"]
+            assert torch.equal(got[sgi][:, rpb:], x0[:, rpb:]) and torch.equal(got[sgi][:, :, N:], x0[:, :, N:]), (case, "wrote outside its rows / columns")

@@ -119,15 +119,12 @@ def test_layernorm_fixed_width_path_equals_generic(gpu):
     x = _randn((B, S, D), 1, 2.0).to(gpu)
     mod = _randn((B, 6 * D), 2, 0.3).to(gpu)
     outs = {}
-    try:
-        for generic in (1, 0):
-            ops.set_option("ln_generic", generic)
+    for generic in (1, 0):
+        with ops.options(ln_generic=generic):
             y = torch.full((B * (S - St), D + 64), 7.0, dtype=torch.bfloat16, device=gpu)
             ops.layernorm(x.view(-1)[St * D:], y, B * (S - St), D, scale=mod.view(-1)[4 * D:], shift=mod.view(-1)[3 * D:], ldx=D,
                           rows_per_batch=S - St, x_batch_stride=S * D, ld_mod=6 * D, ldy=D + 64)
-            outs[generic] = y.cpu()
-    finally:
-        ops.set_option("ln_generic", 0)
+        outs[generic] = y.cpu()
     assert torch.equal(outs[0], outs[1])
     assert (outs[0][:, D:] == 7.0).all()
 
@@ -240,16 +237,11 @@ def test_attention_schedules_are_bit_identical(gpu):
     else:
         with pytest.raises(RuntimeError, match="experiments"):
             ops.set_option("attn_sched", 3)
-    try:
-        for sched, w4, tune, q64 in combos:
-            ops.set_option("attn_sched", sched); ops.set_option("attn_w4", w4); ops.set_option("attn_tune", tune)
-            ops.set_option("attn_q64", q64)
+    for sched, w4, tune, q64 in combos:
+        with ops.options(attn_sched=sched, attn_w4=w4, attn_tune=tune, attn_q64=q64):
             o = torch.full((B, S, D), float("nan"), dtype=torch.bfloat16, device=gpu)
             ops.attention(qkv, qkv.view(-1)[D:], vt, o, B, S, H, 3 * D, S * 3 * D, D, S * D, 1 / math.sqrt(128))
-            outs[(sched, w4, tune, q64)] = o.cpu()
-    finally:
-        ops.set_option("attn_sched", 2); ops.set_option("attn_w4", 0); ops.set_option("attn_tune", 2)   # the library's defaults
-        ops.set_option("attn_q64", 0)
+        outs[(sched, w4, tune, q64)] = o.cpu()
     ref = outs[(0, 0, 0, 2)]
     assert torch.isfinite(ref.float()).all()
     for key, o in outs.items():
@@ -276,26 +268,23 @@ def test_attention_q64_with_fused_q_prep_equals_the_8_wave_kernel(gpu, B, S, H, 
     ops.k_norm_rope_vt(qkv, vt, w[1], w[3], cos, sin, B, S, H, 3 * D, s_txt)
 
     def run(q64, gen=1):
-        ops.set_option("attn_q64", q64); ops.set_option("attn_gen", gen)
-        o = torch.full((B, S, D), float("nan"), device=gpu, dtype=torch.bfloat16)
-        ops.attention_qprep(qkv, qkv.view(-1)[D:], vt, o, B, S, H, 3 * D, S * 3 * D, D, S * D, 1 / math.sqrt(128), w[0], w[2], cos, sin, s_txt)
+        with ops.options(attn_q64=q64, attn_gen=gen):
+            o = torch.full((B, S, D), float("nan"), device=gpu, dtype=torch.bfloat16)
+            ops.attention_qprep(qkv, qkv.view(-1)[D:], vt, o, B, S, H, 3 * D, S * 3 * D, D, S * D, 1 / math.sqrt(128), w[0], w[2], cos, sin, s_txt)
         return o.cpu()
-    try:
-        ref = run(2)
-        assert torch.isfinite(ref.float()).all()
-        # "attn_gen" 1: the hand-placed kernel; 2: round 6's generated stream without the fold — the same float operations in the same order
-        for gen in (1, 2):
-            for i in range(5):
-                got = run(1, gen)
-                assert torch.isfinite(got.float()).all(), f"attn_gen {gen}, launch {i}: {torch.isnan(got.float()).any(-1).sum().item()} rows with NaN"
-                assert torch.equal(got, ref), (gen, i)
-        # 0: the product's choice — the generated stream WITH the fold: deterministic, finite, and as close to the 8-wave kernel as two bf16
-        # evaluations of one attention are to each other
-        fold = [run(1, 0) for _ in range(3)]
-        assert torch.isfinite(fold[0].float()).all() and torch.equal(fold[0], fold[1]) and torch.equal(fold[0], fold[2])
-        assert _rel(fold[0], ref) < 8e-3, _rel(fold[0], ref)
-    finally:
-        ops.set_option("attn_q64", 0); ops.set_option("attn_gen", 0)
+    ref = run(2)
+    assert torch.isfinite(ref.float()).all()
+    # "attn_gen" 1: the hand-placed kernel; 2: round 6's generated stream without the fold — the same float operations in the same order
+    for gen in (1, 2):
+        for i in range(5):
+            got = run(1, gen)
+            assert torch.isfinite(got.float()).all(), f"attn_gen {gen}, launch {i}: {torch.isnan(got.float()).any(-1).sum().item()} rows with NaN"
+            assert torch.equal(got, ref), (gen, i)
+    # 0: the product's choice — the generated stream WITH the fold: deterministic, finite, and as close to the 8-wave kernel as two bf16
+    # evaluations of one attention are to each other
+    fold = [run(1, 0) for _ in range(3)]
+    assert torch.isfinite(fold[0].float()).all() and torch.equal(fold[0], fold[1]) and torch.equal(fold[0], fold[2])
+    assert _rel(fold[0], ref) < 8e-3, _rel(fold[0], ref)
 
 
 @pytest.mark.parametrize("B,S,H,s_txt,qprep", [(2, 1150, 4, 300, True), (1, 1100, 8, 0, False), (2, 5337, 4, 1241, True), (1, 4130, 8, 0, False),
@@ -321,15 +310,14 @@ def test_attention_q64_walking_its_items_equals_one_item_per_workgroup(gpu, B, S
         ops.qk_norm_rope_vt(qkv, vt, None, None, None, None, None, None, B, S, H, 3 * D, 0)
 
     def run(walk, gen=1):
-        ops.set_option("attn_walk", walk); ops.set_option("attn_gen", gen)
-        o = torch.full((B, S, D), float("nan"), device=gpu, dtype=torch.bfloat16)
-        if qprep:
-            ops.attention_qprep(qkv, qkv.view(-1)[D:], vt, o, B, S, H, 3 * D, S * 3 * D, D, S * D, 1 / math.sqrt(128), w[0], w[2], cos, sin, s_txt)
-        else:
-            ops.attention(qkv, qkv.view(-1)[D:], vt, o, B, S, H, 3 * D, S * 3 * D, D, S * D, 1 / math.sqrt(128))
+        with ops.options(attn_walk=walk, attn_gen=gen):
+            o = torch.full((B, S, D), float("nan"), device=gpu, dtype=torch.bfloat16)
+            if qprep:
+                ops.attention_qprep(qkv, qkv.view(-1)[D:], vt, o, B, S, H, 3 * D, S * 3 * D, D, S * D, 1 / math.sqrt(128), w[0], w[2], cos, sin, s_txt)
+            else:
+                ops.attention(qkv, qkv.view(-1)[D:], vt, o, B, S, H, 3 * D, S * 3 * D, D, S * D, 1 / math.sqrt(128))
         return o.cpu()
-    try:
-        ops.set_option("attn_q64", 1)
+    with ops.options(attn_q64=1):
         ref = run(2)
         assert torch.isfinite(ref.float()).all()
         # the hand-placed kernel (1) and round 6's generated stream without the fold (2: it runs where the tiles pair up, the hand-placed
@@ -344,8 +332,6 @@ def test_attention_q64_walking_its_items_equals_one_item_per_workgroup(gpu, B, S
         assert torch.isfinite(ref0.float()).all() and _rel(ref0, ref) < 8e-3
         for walk in (8, 16, 0):
             assert torch.equal(run(walk, 0), ref0), ("attn_gen 0", walk)
-    finally:
-        ops.set_option("attn_q64", 0); ops.set_option("attn_walk", 0); ops.set_option("attn_gen", 0)
 
 
 @pytest.mark.parametrize("B,S,H,s_txt,hot", [(2, 1150, 4, 300, False), (1, 1089, 8, 100, True), (2, 5337, 4, 1241, True), (1, 4300, 2, 100, False)])
@@ -390,17 +376,14 @@ def test_attention_q64_fold_is_as_close_to_float64_as_the_unfolded_kernels(gpu, 
     ops.k_norm_rope_vt(x, vt, w[1], w[3], cos, sin, B, S, H, 3 * D, s_txt)
 
     def run(gen):
-        ops.set_option("attn_gen", gen)
-        o = torch.full((B, S, D), float("nan"), device=gpu, dtype=torch.bfloat16)
-        ops.attention_qprep(x, x.view(-1)[D:], vt, o, B, S, H, 3 * D, S * 3 * D, D, S * D, scale, w[0], w[2], cos, sin, s_txt)
+        with ops.options(attn_gen=gen):
+            o = torch.full((B, S, D), float("nan"), device=gpu, dtype=torch.bfloat16)
+            ops.attention_qprep(x, x.view(-1)[D:], vt, o, B, S, H, 3 * D, S * 3 * D, D, S * D, scale, w[0], w[2], cos, sin, s_txt)
         return o
-    try:
-        ops.set_option("attn_q64", 1)
+    with ops.options(attn_q64=1):
         from domain_rag_amd import _lib
         assert _lib.load().drag_attention_bf16_choice(S, 0, 1) == 641
         plain, fold = run(2), run(0)
-    finally:
-        ops.set_option("attn_q64", 0); ops.set_option("attn_gen", 0)
     assert torch.isfinite(fold.float()).all()
     vmax = ref.abs().max().item()
     e_plain = (plain.double() - ref).abs().max().item() / vmax
@@ -431,70 +414,64 @@ def test_attention_hot_key_in_every_lane_half(gpu, S):
     last = (S - 1) // 64
     # tile 5 at many positions; the first tile (maxima from the prologue) and the last one (ragged for S = 1087: 63 keys) at a few
     where = [(5, pos) for pos in list(range(0, 64, 3)) + [4, 5, 7, 13, 37, 63]] + [(t, pos) for t in (0, 1, last) for pos in (0, 6, 33, 44, (S - 1) % 64)]
-    try:
-        for tile, pos in where:
-            x = base.clone()
-            hot = tile * 64 + pos
-            x[0, hot, D:2 * D] = qdir * 300.0
-            qkv = x.bfloat16().to(gpu)
-            vt = torch.empty(B, H, 128, (S + 63) // 64 * 64, device=gpu, dtype=torch.bfloat16)
-            ops.qk_norm_rope_vt(qkv, vt, None, None, None, None, None, None, B, S, H, 3 * D, 0)
-            outs = {}
-            # 2: the 8-wave family; 1: the 64-query kernel, hand-placed ("attn_gen" 1) and as round 6's generated stream (3 here = "attn_gen" 2;
-            # S = 1087 pairs its 18 tiles up, S = 4160 has 65: the hand-placed kernel runs there whatever the switch says)
-            for q64 in (2, 1, 3):
-                ops.set_option("attn_q64", min(q64, 1) if q64 != 2 else 2); ops.set_option("attn_gen", 2 if q64 == 3 else 1)
+    for tile, pos in where:
+        x = base.clone()
+        hot = tile * 64 + pos
+        x[0, hot, D:2 * D] = qdir * 300.0
+        qkv = x.bfloat16().to(gpu)
+        vt = torch.empty(B, H, 128, (S + 63) // 64 * 64, device=gpu, dtype=torch.bfloat16)
+        ops.qk_norm_rope_vt(qkv, vt, None, None, None, None, None, None, B, S, H, 3 * D, 0)
+        outs = {}
+        # 2: the 8-wave family; 1: the 64-query kernel, hand-placed ("attn_gen" 1) and as round 6's generated stream (3 here = "attn_gen" 2;
+        # S = 1087 pairs its 18 tiles up, S = 4160 has 65: the hand-placed kernel runs there whatever the switch says)
+        for q64 in (2, 1, 3):
+            with ops.options(attn_q64=min(q64, 1) if q64 != 2 else 2, attn_gen=2 if q64 == 3 else 1):
                 o = torch.full((B, S, D), float("nan"), device=gpu, dtype=torch.bfloat16)
                 ops.attention(qkv, qkv.view(-1)[D:], vt, o, B, S, H, 3 * D, S * 3 * D, D, S * D, 1 / math.sqrt(128))
-                outs[q64] = o.float().cpu()[0]
-            for q64, o in outs.items():
-                assert torch.isfinite(o).all(), (tile, pos, q64, int(torch.isnan(o).any(1).sum()))
-                # rows with a usual q component along qdir put all their mass on the hot key: column hot % 128 of the one-hot V
-                mass = o[:, hot % 128]
-                assert (mass > 0.99).float().mean().item() > 0.95, (tile, pos, q64, mass.min().item())
-            assert torch.equal(outs[1], outs[2]) and torch.equal(outs[3], outs[2]), (tile, pos)
-        # every schedule / block shape of the 8-wave family on two hot positions (one per lane half)
-        for tile, pos in [(5, 5), (5, 36)]:
-            x = base.clone()
-            hot = tile * 64 + pos
-            x[0, hot, D:2 * D] = qdir * 300.0
-            qkv = x.bfloat16().to(gpu)
-            vt = torch.empty(B, H, 128, (S + 63) // 64 * 64, device=gpu, dtype=torch.bfloat16)
-            ops.qk_norm_rope_vt(qkv, vt, None, None, None, None, None, None, B, S, H, 3 * D, 0)
-            ops.set_option("attn_q64", 2)
-            got = {}
-            for sched, w4, tune in [(2, 0, 2), (0, 0, 0), (1, 0, 0), (2, 0, 3), (1, 1, 2), (2, 1, 0)]:
-                ops.set_option("attn_sched", sched); ops.set_option("attn_w4", w4); ops.set_option("attn_tune", tune)
+            outs[q64] = o.float().cpu()[0]
+        for q64, o in outs.items():
+            assert torch.isfinite(o).all(), (tile, pos, q64, int(torch.isnan(o).any(1).sum()))
+            # rows with a usual q component along qdir put all their mass on the hot key: column hot % 128 of the one-hot V
+            mass = o[:, hot % 128]
+            assert (mass > 0.99).float().mean().item() > 0.95, (tile, pos, q64, mass.min().item())
+        assert torch.equal(outs[1], outs[2]) and torch.equal(outs[3], outs[2]), (tile, pos)
+    # every schedule / block shape of the 8-wave family on two hot positions (one per lane half)
+    for tile, pos in [(5, 5), (5, 36)]:
+        x = base.clone()
+        hot = tile * 64 + pos
+        x[0, hot, D:2 * D] = qdir * 300.0
+        qkv = x.bfloat16().to(gpu)
+        vt = torch.empty(B, H, 128, (S + 63) // 64 * 64, device=gpu, dtype=torch.bfloat16)
+        ops.qk_norm_rope_vt(qkv, vt, None, None, None, None, None, None, B, S, H, 3 * D, 0)
+        got = {}
+        for sched, w4, tune in [(2, 0, 2), (0, 0, 0), (1, 0, 0), (2, 0, 3), (1, 1, 2), (2, 1, 0)]:
+            with ops.options(attn_q64=2, attn_sched=sched, attn_w4=w4, attn_tune=tune):
                 o = torch.full((B, S, D), float("nan"), device=gpu, dtype=torch.bfloat16)
                 ops.attention(qkv, qkv.view(-1)[D:], vt, o, B, S, H, 3 * D, S * 3 * D, D, S * D, 1 / math.sqrt(128))
-                got[(sched, w4, tune)] = o.float().cpu()[0]
-            for key, o in got.items():
-                assert torch.isfinite(o).all() and torch.equal(o, got[(2, 0, 2)]), (tile, pos, key)
-        ops.set_option("attn_sched", 2); ops.set_option("attn_w4", 0); ops.set_option("attn_tune", 2)
-        # the fused q preparation: q and k are RMS-normalised, so a key parallel to every query sits 16 octaves up — the deferred rescale
-        # (threshold 8) fires at its tile, in whichever lane half it lives
-        ones = torch.ones(128).bfloat16().to(gpu)
-        cos, sin = torch.ones(S, 64, device=gpu), torch.zeros(S, 64, device=gpu)
-        for tile, pos in [(5, 2), (5, 5), (5, 36), (5, 47), (1, 4), (last, 6)]:
-            x = base.clone()
-            x[0, :, :D] = qdir * 4.0 + torch.randn(S, D, generator=g) * 0.05
-            hot = tile * 64 + pos
-            x[0, hot, D:2 * D] = qdir * 4.0
-            qkv = x.bfloat16().to(gpu)
-            vt = torch.empty(B, H, 128, (S + 63) // 64 * 64, device=gpu, dtype=torch.bfloat16)
-            ops.k_norm_rope_vt(qkv, vt, ones, ones, cos, sin, B, S, H, 3 * D, 0)
-            for q64 in (2, 1, 3, 4):          # 3: the generated stream without the fold, 4: with it (the product's choice)
-                ops.set_option("attn_q64", 2 if q64 == 2 else 1); ops.set_option("attn_gen", {2: 1, 1: 1, 3: 2, 4: 0}[q64])
+            got[(sched, w4, tune)] = o.float().cpu()[0]
+        for key, o in got.items():
+            assert torch.isfinite(o).all() and torch.equal(o, got[(2, 0, 2)]), (tile, pos, key)
+    # the fused q preparation: q and k are RMS-normalised, so a key parallel to every query sits 16 octaves up — the deferred rescale
+    # (threshold 8) fires at its tile, in whichever lane half it lives
+    ones = torch.ones(128).bfloat16().to(gpu)
+    cos, sin = torch.ones(S, 64, device=gpu), torch.zeros(S, 64, device=gpu)
+    for tile, pos in [(5, 2), (5, 5), (5, 36), (5, 47), (1, 4), (last, 6)]:
+        x = base.clone()
+        x[0, :, :D] = qdir * 4.0 + torch.randn(S, D, generator=g) * 0.05
+        hot = tile * 64 + pos
+        x[0, hot, D:2 * D] = qdir * 4.0
+        qkv = x.bfloat16().to(gpu)
+        vt = torch.empty(B, H, 128, (S + 63) // 64 * 64, device=gpu, dtype=torch.bfloat16)
+        ops.k_norm_rope_vt(qkv, vt, ones, ones, cos, sin, B, S, H, 3 * D, 0)
+        for q64 in (2, 1, 3, 4):          # 3: the generated stream without the fold, 4: with it (the product's choice)
+            with ops.options(attn_q64=2 if q64 == 2 else 1, attn_gen={2: 1, 1: 1, 3: 2, 4: 0}[q64]):
                 o = torch.full((B, S, D), float("nan"), device=gpu, dtype=torch.bfloat16)
                 ops.attention_qprep(qkv, qkv.view(-1)[D:], vt, o, B, S, H, 3 * D, S * 3 * D, D, S * D, 1 / math.sqrt(128), ones, ones, cos, sin, 0)
-                outs[q64] = o.float().cpu()[0]
-            assert all(torch.isfinite(outs[q]).all() for q in (1, 2, 3, 4)), (tile, pos)
-            for q in (1, 4):
-                assert (outs[q][:, hot % 128] > 0.9).float().mean().item() > 0.95, (tile, pos, q, outs[q][:, hot % 128].min().item())
-            assert torch.equal(outs[1], outs[2]) and torch.equal(outs[3], outs[2]), ("fused q preparation", tile, pos)
-    finally:
-        ops.set_option("attn_q64", 0); ops.set_option("attn_sched", 2); ops.set_option("attn_w4", 0); ops.set_option("attn_tune", 2)
-        ops.set_option("attn_gen", 0)
+            outs[q64] = o.float().cpu()[0]
+        assert all(torch.isfinite(outs[q]).all() for q in (1, 2, 3, 4)), (tile, pos)
+        for q in (1, 4):
+            assert (outs[q][:, hot % 128] > 0.9).float().mean().item() > 0.95, (tile, pos, q, outs[q][:, hot % 128].min().item())
+        assert torch.equal(outs[1], outs[2]) and torch.equal(outs[3], outs[2]), ("fused q preparation", tile, pos)
 
 
 @pytest.mark.parametrize("B,S,H,s_txt", [(1, 4300, 8, 1241), (2, 4224, 8, 0), (3, 4161, 8, 512), (1, 5337, 24, 1241)])
@@ -528,16 +505,13 @@ def test_persistent_attention_equals_the_one_item_kernel(gpu, B, S, H, s_txt):
         else:
             ops.attention(qkv, qkv.view(-1)[D:], vt, o, B, S, H, 3 * D, S * 3 * D, D, S * D, scale)
         return o.cpu()
-    try:
-        ops.set_option("attn_persist", 0)
+    with ops.options(attn_persist=0):
         ref = {qp: run(qp) for qp in (False, True)}
-        assert all(torch.isfinite(r.float()).all() for r in ref.values())
-        for slots in (3, 5, 1):
-            ops.set_option("attn_persist", slots)
+    assert all(torch.isfinite(r.float()).all() for r in ref.values())
+    for slots in (3, 5, 1):
+        with ops.options(attn_persist=slots):
             for qp in (False, True):
                 assert torch.equal(run(qp), ref[qp]), (slots, qp)
-    finally:
-        ops.set_option("attn_persist", 0)
 
 
 def test_attention_tensors_beyond_4_gib(gpu):
@@ -607,11 +581,8 @@ def test_attention_row_major_v_equals_vt_path(gpu, B, S, H, s_txt):
     ops.attention_v(b2, b2.view(-1)[D:], b2.view(-1)[2 * D:], o_q, B, S, H, 3 * D, S * 3 * D, D, S * D, scale,
                     w[0], w[2], cos, sin, s_txt)
     o_qvt = out_buf()           # the fused q preparation sums the squares in another order than the pass: compare like with like
-    ops.set_option("attn_gen", 2)       # (without round 6's fold, which is its own evaluation: the V^T route's generated stream, same operations)
-    try:
+    with ops.options(attn_gen=2):       # (without round 6's fold, which is its own evaluation: the V^T route's generated stream, same operations)
         ops.attention_qprep(b2, b2.view(-1)[D:], vt, o_qvt, B, S, H, 3 * D, S * 3 * D, D, S * D, scale, w[0], w[2], cos, sin, s_txt)
-    finally:
-        ops.set_option("attn_gen", 0)
     assert torch.equal(o_q, o_qvt)
     assert _rel(o_q.cpu(), o_vt.cpu()) < 1e-2
     with pytest.raises(RuntimeError, match="or none"):
@@ -634,14 +605,11 @@ def test_topk_bit_exact(gpu, N, Q, k):
     qs = rng.standard_normal((Q, 512)).astype(np.float32)
     qs /= np.linalg.norm(qs, axis=1, keepdims=True)
     Dr, Ir = oret.cosine_topk(corpus, qs, k)
-    try:
-        for path in (0, 1):          # 0: by policy (two launches through the group maxima where k <= 128 and 8192 < N <= 131072), 1: sampled threshold
-            ops.set_option("topk_path", path)
+    for path in (0, 1):          # 0: by policy (two launches through the group maxima where k <= 128 and 8192 < N <= 131072), 1: sampled threshold
+        with ops.options(topk_path=path):
             D, I = ops.cosine_topk(torch.from_numpy(corpus).to(gpu), torch.from_numpy(qs).to(gpu), k)
             assert np.array_equal(I.cpu().numpy(), Ir), path
             assert np.array_equal(D.cpu().numpy().view(np.uint32), Dr.view(np.uint32)), path
-    finally:
-        ops.set_option("topk_path", 0)
 
 
 @pytest.mark.parametrize("N,Q,k", [(8193, 1, 128), (8193, 3, 100), (8208, 1, 1), (131072, 1, 100), (131072, 17, 128), (131067, 64, 100),
@@ -676,14 +644,11 @@ def test_topk_two_launch_path_at_its_limits(gpu, N, Q, k):
     qs = (u[None] * (1 + 0.1 * np.arange(Q)[:, None]) + 0.05 * rng.standard_normal((Q, d))).astype(np.float32)
     Dr, Ir = oret.cosine_topk(corpus, qs, k)
     cd, qd = torch.from_numpy(corpus).to(gpu), torch.from_numpy(qs).to(gpu)
-    try:
-        for path in (0, 1, 2):          # policy | sampled threshold | group maxima wherever the form applies (1, 2, 4, 8 groups per key)
-            ops.set_option("topk_path", path)
+    for path in (0, 1, 2):          # policy | sampled threshold | group maxima wherever the form applies (1, 2, 4, 8 groups per key)
+        with ops.options(topk_path=path):
             D, I = ops.cosine_topk(cd, qd, k)
             assert np.array_equal(I.cpu().numpy(), Ir), path
             assert np.array_equal(D.cpu().numpy().view(np.uint32), Dr.view(np.uint32)), path
-    finally:
-        ops.set_option("topk_path", 0)
 
 
 def test_topk_ties_and_padding(gpu):
@@ -722,13 +687,10 @@ def test_topk_when_the_sample_misrepresents_the_corpus(gpu):
         sampled[i * stride * 16: i * stride * 16 + 16] = True
     corpus[sampled] = -10.0 * qs.sum(0)                        # the sampled rows: strongly anti-aligned with every query
     Dr, Ir = oret.cosine_topk(corpus, qs, k)
-    try:
-        for path in (1, 0):                                    # the sampled-threshold form this corpus is built against, then the policy's
-            ops.set_option("topk_path", path)
+    for path in (1, 0):                                    # the sampled-threshold form this corpus is built against, then the policy's
+        with ops.options(topk_path=path):
             D, I = ops.cosine_topk(torch.from_numpy(corpus).to(gpu), torch.from_numpy(qs).to(gpu), k)
             assert np.array_equal(I.cpu().numpy(), Ir) and np.array_equal(D.cpu().numpy().view(np.uint32), Dr.view(np.uint32)), path
-    finally:
-        ops.set_option("topk_path", 0)
     same = np.tile(rng.standard_normal((1, 512)).astype(np.float32), (20000, 1))
     D, I = ops.cosine_topk(torch.from_numpy(same).to(gpu), torch.from_numpy(qs).to(gpu), k)
     assert (I.cpu().numpy() == np.arange(k)[None]).all() and (D.cpu().numpy() == D.cpu().numpy()[:, :1]).all()
@@ -766,27 +728,20 @@ def test_topk_threshold_and_selection_variants_give_the_same_answer(gpu):
     g = torch.Generator(device=gpu).manual_seed(9)
     corpus = torch.randn(50021, 512, generator=g, device=gpu)
     q = torch.randn(53, 512, generator=g, device=gpu)
-    try:
-        ref = {k: ops.cosine_topk(corpus, q, k) for k in (1, 100, 128, 129)}
-        sc0 = ops.cosine_scores(corpus, q)
-        variants = [{"topk_dense_sample": 1}, {"topk_select": 256}, {"topk_select": 1024}, {"topk_grid": 1024, "topk_depth": 3},
-                    {"topk_dense_sample": 1, "topk_select": 1024, "topk_grid": 2048}, {"topk_grid": 16},     # (a grid below one unit of workgroups is clamped)
-                    {"topk_path": 1}, {"topk_path": 1, "topk_dense_sample": 1}, {"topk_path": 1, "topk_select": 256, "topk_grid": 1024},
-                    {"topk_grid": 2048, "topk_depth": 3}]
-        if ops.experiments_built():
-            variants += [{"topk_qt": 2}, {"topk_qt": 4}, {"topk_qt": 4, "topk_grid": 1024}]
-        for opts in variants:
-            for name, v in opts.items():
-                ops.set_option(name, v)
+    ref = {k: ops.cosine_topk(corpus, q, k) for k in (1, 100, 128, 129)}
+    sc0 = ops.cosine_scores(corpus, q)
+    variants = [{"topk_dense_sample": 1}, {"topk_select": 256}, {"topk_select": 1024}, {"topk_grid": 1024, "topk_depth": 3},
+                {"topk_dense_sample": 1, "topk_select": 1024, "topk_grid": 2048}, {"topk_grid": 16},     # (a grid below one unit of workgroups is clamped)
+                {"topk_path": 1}, {"topk_path": 1, "topk_dense_sample": 1}, {"topk_path": 1, "topk_select": 256, "topk_grid": 1024},
+                {"topk_grid": 2048, "topk_depth": 3}]
+    if ops.experiments_built():
+        variants += [{"topk_qt": 2}, {"topk_qt": 4}, {"topk_qt": 4, "topk_grid": 1024}]
+    for opts in variants:
+        with ops.options(**opts):
             for k, (D0, I0) in ref.items():
                 D, I = ops.cosine_topk(corpus, q, k)
                 assert torch.equal(D, D0) and torch.equal(I, I0), (opts, k)
             assert torch.equal(ops.cosine_scores(corpus, q)[:, :50021], sc0[:, :50021]), opts
-            for name in opts:
-                ops.set_option(name, 0)
-    finally:
-        for name in ("topk_dense_sample", "topk_select", "topk_grid", "topk_depth", "topk_qt", "topk_path"):
-            ops.set_option(name, 0)
 
 
 def test_l2_normalize(gpu):
@@ -836,21 +791,21 @@ def test_gemm_t256_identity_and_epilogues(gpu):
 
 def test_gemm_t256_race_screen(gpu):
     """the phased schedule keeps LDS-DMA in flight across barriers: results must be bit-identical run to run and equal
-    to the simple 128x128 kernel's (same k-order per output element -> same fp32 sums)"""
-    import os
-    from domain_rag_amd import ops
+    to the simple 128x128 kernel's (same k-order per output element -> same fp32 sums).  "gemm_t128" withdraws the 256x256 kernels from the
+    tile policy; the policy query says, per shape, that the two sides of the comparison are different kernels"""
+    from domain_rag_amd import _lib, ops
+    choice = _lib.load().drag_gemm_bf16_choice
     g = torch.Generator().manual_seed(3)
     for (M, N, K) in [(8192, 4096, 4096), (42696 // 4, 3072, 15360 // 4)]:
         a = torch.randn(M, K, generator=g).bfloat16().to(gpu)
         w = (torch.randn(N, K, generator=g) * 0.02).bfloat16().to(gpu)
+        assert choice(M, 0, N, K) in (2, 3)
         ref = ops.gemm(a, w).clone()
         for _ in range(6):
             assert torch.equal(ops.gemm(a, w), ref)
-        os.environ["DRAG_GEMM_T128"] = "1"
-        try:
+        with ops.options(gemm_t128=1):
+            assert choice(M, 0, N, K) not in (2, 3)
             small = ops.gemm(a, w)
-        finally:
-            del os.environ["DRAG_GEMM_T128"]
         assert torch.equal(small, ref)
 
 
@@ -871,16 +826,12 @@ def test_gemm_staged_epilogue_equals_fragment_epilogue(gpu):
     """the LDS-transposed (16-B store) epilogue and the fragment-layout (8-B store) one must agree bit for bit:
     same fp32 sums, same rounding points — plain, bias+act, gated residual over batched rows whose tiles straddle
     batch boundaries, edge tiles (N % 256 != 0, M % 256 != 0), both tile sizes"""
-    import os
     from domain_rag_amd import ops
 
     def both(fn):
         wide = fn().clone()
-        os.environ["DRAG_GEMM_NARROW"] = "1"
-        try:
+        with ops.options(gemm_narrow=1):
             narrow = fn().clone()
-        finally:
-            del os.environ["DRAG_GEMM_NARROW"]
         assert torch.equal(wide, narrow)
         return wide
 
@@ -926,16 +877,12 @@ def test_gemm_kernels_are_bit_identical(gpu, M, N, K):
         return [o.cpu() for o in outs]
 
     codes = [1, 42, 43, 22, 23, 24, 13, 14, 113, 123, 133, 143, 0] + ([2, 3] if N >= 256 and K >= 256 else [])      # 1xx: 192-column tiles; 3: the 4-wave persistent kernel (where K % 128 == 0, else the 8-wave one)
-    try:
-        res = {}
-        for code in codes:
-            ops.set_option("gemm_kernel", code)
+    res = {}
+    for code in codes:
+        with ops.options(gemm_kernel=code):
             res[code] = run_all()
-        ops.set_option("gemm_kernel", 44)
-        with pytest.raises(RuntimeError, match="not built"):
-            ops.gemm(a, w)
-    finally:
-        ops.set_option("gemm_kernel", 0)
+    with ops.options(gemm_kernel=44), pytest.raises(RuntimeError, match="not built"):
+        ops.gemm(a, w)
     for code in codes[1:]:
         for i, (x, y) in enumerate(zip(res[1], res[code])):
             assert torch.equal(x, y), (code, i)
@@ -964,17 +911,13 @@ def test_specialised_epilogue_equals_the_general_one(gpu, M, N, K, rpb):
         return [o.cpu() for o in outs]
 
     codes = [0, 1, 43, 23, 14] + ([2, 3] if N >= 256 and K >= 256 else [])
-    try:
-        for code in codes:
-            ops.set_option("gemm_kernel", code)
-            ops.set_option("gemm_epilogue", 1)
+    for code in codes:
+        with ops.options(gemm_kernel=code, gemm_epilogue=1):
             ref = run_all()
-            ops.set_option("gemm_epilogue", 0)
+        with ops.options(gemm_kernel=code, gemm_epilogue=0):
             got = run_all()
-            for i, (x, y) in enumerate(zip(ref, got)):
-                assert torch.isfinite(x.float()).all() and torch.equal(x, y), (code, i)
-    finally:
-        ops.set_option("gemm_kernel", 0); ops.set_option("gemm_epilogue", 0)
+        for i, (x, y) in enumerate(zip(ref, got)):
+            assert torch.isfinite(x.float()).all() and torch.equal(x, y), (code, i)
 
 
 @pytest.mark.parametrize("M,N,K,rpb", [(1024, 768, 512, 256), (600, 520, 1024, 300), (2560, 512, 256, 1280)])
@@ -999,10 +942,9 @@ def test_gemm_epilogue_rounding_order_is_torchs_bit_for_bit(gpu, M, N, K, rpb):
     assert exact.abs().max() < 2048 and (exact.float().double() == exact).all()
     ad, wd, bd, gd = a.to(gpu), w.to(gpu), bias.to(gpu), gate.to(gpu)
     codes = [0, 1, 43, 23, 14] + ([2] if N >= 256 and K >= 256 else [])
-    try:
-        for code in codes:
-            for epi in (0, 1):
-                ops.set_option("gemm_kernel", code); ops.set_option("gemm_epilogue", epi)
+    for code in codes:
+        for epi in (0, 1):
+            with ops.options(gemm_kernel=code, gemm_epilogue=epi):
                 got = {"bias": ops.gemm(ad, wd, bias=bd), "plain": ops.gemm(ad, wd)}
                 x = resid.to(gpu).clone()
                 ops.gemm(ad, wd, out=x, bias=bd, M=M, lda=K, ldc=N, resid=x)
@@ -1010,12 +952,10 @@ def test_gemm_epilogue_rounding_order_is_torchs_bit_for_bit(gpu, M, N, K, rpb):
                 y = resid.to(gpu).clone()
                 ops.gemm(ad, wd, out=y, bias=bd, M=M, lda=K, ldc=N, c_rows_per_batch=rpb, c_batch_stride=rpb * N, gate=gd, resid=y, ldg=N)
                 got["gate"] = y
-                for name, t in got.items():
-                    t = t.cpu()
-                    same = (t == want[name]).float().mean().item()
-                    assert torch.equal(t, want[name]), (code, epi, name, same, (t.float() - want[name].float()).abs().max().item())
-    finally:
-        ops.set_option("gemm_kernel", 0); ops.set_option("gemm_epilogue", 0)
+            for name, t in got.items():
+                t = t.cpu()
+                same = (t == want[name]).float().mean().item()
+                assert torch.equal(t, want[name]), (code, epi, name, same, (t.float() - want[name].float()).abs().max().item())
 
 
 @pytest.mark.parametrize("M1,M2,N,K", [(1024, 512, 768, 256), (1000, 77, 520, 192), (300, 1300, 1536, 320), (40, 24, 384, 128), (2304, 1100, 1024, 256)])
@@ -1055,22 +995,17 @@ def test_gemm_pair_equals_two_gemms(gpu, M1, M2, N, K):
 
     ref = forms(lambda f, s: (ops.gemm(**f), ops.gemm(**s)))
     assert (ref[0][M1:] == 7.0).all() and (ref[1][M2:] == 7.0).all()
-    try:
-        ops.set_option("gemm_pair", 2)                     # always one launch
+    with ops.options(gemm_pair=2):                     # always one launch
         for code in (0, 1, 2, 23, 32, 14, 123):
             if code == 123 and N % 192:
                 continue
-            ops.set_option("gemm_kernel", code)
-            got = forms(ops.gemm_pair)
+            with ops.options(gemm_kernel=code):
+                got = forms(ops.gemm_pair)
             for i, (x, y) in enumerate(zip(ref, got)):
                 assert torch.equal(x, y), (code, i)
-        ops.set_option("gemm_kernel", 0)
-        ops.set_option("gemm_pair", 1)                     # never merged: the library issues the two launches itself
+    with ops.options(gemm_kernel=0, gemm_pair=1):          # never merged: the library issues the two launches itself
         got = forms(ops.gemm_pair)
-        assert all(torch.equal(x, y) for x, y in zip(ref, got))
-    finally:
-        ops.set_option("gemm_kernel", 0)
-        ops.set_option("gemm_pair", 0)
+    assert all(torch.equal(x, y) for x, y in zip(ref, got))
     with pytest.raises(ValueError, match="share N and K"):
         ops.gemm_pair(dict(a=a1, w=w1), dict(a=a2, w=w2[: N - 64]))
     with pytest.raises(ValueError, match="activation"):
@@ -1116,11 +1051,8 @@ def test_gemm_w4_experiment_is_bit_identical(gpu, M, N, K):
     ref = ops.gemm(a, w, bias=b)
     ref2 = ops.gemm(a, w, bias=b, gate=g, resid=r, ldg=N)
     for kern in (400, 401):
-        ops.set_option("gemm_kernel", kern)
-        try:
+        with ops.options(gemm_kernel=kern):
             got, got2 = ops.gemm(a, w, bias=b), ops.gemm(a, w, bias=b, gate=g, resid=r, ldg=N)
-        finally:
-            ops.set_option("gemm_kernel", 0)
         assert torch.equal(got, ref) and torch.equal(got2, ref2), kern
 
 
@@ -1154,11 +1086,10 @@ def test_gemm_w4p_equals_the_8_wave_kernel(gpu, M, N, K):
 
     from domain_rag_amd import _lib
     assert _lib.load().drag_gemm_bf16_choice(70000, 0, 1024, 256) == 3 and _lib.load().drag_gemm_bf16_choice(2500, 0, 1100, 1024) != 3
-    try:
-        ops.set_option("gemm_kernel", 2); ref = run_all()
-        ops.set_option("gemm_kernel", 3); got = run_all()
-    finally:
-        ops.set_option("gemm_kernel", 0)
+    with ops.options(gemm_kernel=2):
+        ref = run_all()
+    with ops.options(gemm_kernel=3):
+        got = run_all()
     for i, (x, y) in enumerate(zip(ref, got)):
         assert torch.isfinite(x.float()).all() and torch.equal(x, y), i
 
@@ -1190,17 +1121,16 @@ def test_gemm_split_k_equals_one_launch_to_the_last_bf16_bit_or_so(gpu, M, N, K,
         args, _, _ = ops._gemm_args(a, w, None, kw.get("bias"), kw.get("act", ops.ACT_NONE), 0, None, None, kw.get("out_f32", False), kw.get("M"), 0, 0, None, 0, 0, None, 0,
                                     None, 0, 0)
         return _lib.load().drag_gemm_bf16_splitk_slices(ctypes.byref(args))
-    try:
-        ops.gemm(a[:256], w[:256])                       # (registers the workspace)
-        ops.set_option("gemm_splitk", 0)
+    ops.gemm(a[:256], w[:256])                       # (registers the workspace)
+    with ops.options(gemm_splitk=0):
         assert slices() == (want if (M // 256) * (N // 256) <= 96 and K >= 12288 else 0)
         assert slices(act=ops.ACT_GELU_TANH, bias=b) == 0 and slices(out_f32=True) == 0 and slices(M=M - 8) == 0
-        ops.set_option("gemm_splitk", 1); assert slices() == 0
+    with ops.options(gemm_splitk=1):
+        assert slices() == 0
         ref = run_all()
-        ops.set_option("gemm_splitk", want); assert slices() == want
+    with ops.options(gemm_splitk=want):
+        assert slices() == want
         got = run_all()
-    finally:
-        ops.set_option("gemm_splitk", 0)
     exact = [ref64, ref64 + b.double().cpu(), None, None]
     for i, (x, y) in enumerate(zip(ref, got)):
         assert torch.isfinite(y.float()).all(), i
@@ -1233,15 +1163,14 @@ def test_gemm_pair_split_k_is_one_partial_launch_over_both_problems(gpu, M1, M2,
     def run():
         o1, o2 = ops.gemm_pair(dict(p1, out=torch.empty(M1, N, dtype=torch.bfloat16, device=gpu)), dict(p2, out=torch.empty(M2, N, dtype=torch.bfloat16, device=gpu)))
         return o1.cpu(), o2.cpu()
-    try:
-        ops.gemm(p1["a"][:256], p1["w"][:256])            # (registers the workspace)
-        ops.set_option("gemm_splitk", 1); ref = run()
-        ops.set_option("gemm_splitk", 0); got = run()
+    ops.gemm(p1["a"][:256], p1["w"][:256])            # (registers the workspace)
+    with ops.options(gemm_splitk=1):
+        ref = run()
+    with ops.options(gemm_splitk=0):
+        got = run()
         a1, _, _ = ops._gemm_args(p1["a"], p1["w"], None, None, ops.ACT_NONE, 0, None, None, False, None, 0, 0, None, 0, 0, None, 0, None, 0, 0)
         a2, _, _ = ops._gemm_args(p2["a"], p2["w"], None, None, ops.ACT_NONE, 0, None, None, False, None, 0, 0, None, 0, 0, None, 0, None, 0, 0)
         assert _lib.load().drag_gemm_bf16_pair_splitk_slices(ctypes.byref(a1), ctypes.byref(a2)) >= 2
-    finally:
-        ops.set_option("gemm_splitk", 0)
     for (x, y, pr) in ((ref[0], got[0], p1), (ref[1], got[1], p2)):
         v64 = pr["a"].double() @ pr["w"].double().T + pr["bias"].double()
         exact = (pr["resid"].double() + pr["gate"].double() * v64).cpu()
