@@ -10,6 +10,7 @@ import hashlib
 import importlib.util
 import json
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -53,6 +54,20 @@ class IsaCheckError(RuntimeError):
 
 def _sources() -> list[str]:
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
+
+
+def _included(path: str, seen: set[str] | None = None) -> list[str]:
+    """the headers `path` reaches through #include "..." lines, each resolved relative to the file that names it; one that does not exist
+    (attn_q64_tile_exp.h outside an experiments build, under its #if) is skipped"""
+    seen = set() if seen is None else seen
+    with open(path, errors="replace") as f:
+        names = re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', f.read(), re.M)
+    for name in names:
+        h = os.path.normpath(os.path.join(os.path.dirname(path), name))
+        if h not in seen and os.path.exists(h):
+            seen.add(h)
+            _included(h, seen)
+    return sorted(seen)
 
 
 def _digest(path: str, extra: list[str], compiler: str = "") -> str:
@@ -102,8 +117,6 @@ def build_library(force: bool = False, verbose: bool = True) -> str:
         if not os.path.exists(exp_header) or open(exp_header).read() != r.stdout:
             with open(exp_header, "w") as f:
                 f.write(r.stdout)
-    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
-    headers.append(os.path.join(HERE, "..", "include", "domainrag_hip.h"))
     isa = ISA
     compiler = _compiler_version(isa, hipcc)
     # the checker is part of what an object was built under: editing its rules re-checks (= recompiles) the checked sources
@@ -113,14 +126,18 @@ def build_library(force: bool = False, verbose: bool = True) -> str:
     for src in _sources():
         obj = os.path.join(BUILD, os.path.basename(src)[:-4] + ".o")
         stamp = obj + ".sha"
-        dig = _digest(src, headers + (checker if os.path.basename(src) in isa.CHECKED else []), compiler)
+        deps = _included(src)
+        dig = _digest(src, deps + (checker if os.path.basename(src) in isa.CHECKED else []), compiler)
         objs.append(obj)
         if not force and os.path.exists(obj) and os.path.exists(stamp) and open(stamp).read() == dig:
             continue
-        jobs.append((src, obj, stamp, dig))
+        jobs.append((src, obj, stamp, dig, sum(os.path.getsize(p) for p in [src] + deps)))
+    # the largest sources first (by the bytes the compiler reads: a kernel's body may live in a header), so that the longest compiles
+    # start at once instead of behind the queue
+    jobs.sort(key=lambda job: job[4], reverse=True)
 
     def compile_one(job):
-        src, obj, stamp, dig = job
+        src, obj, stamp, dig = job[:4]
         base = os.path.basename(src)
         wanted = isa.CHECKED.get(base)
         if os.path.exists(stamp):
@@ -170,7 +187,8 @@ def build_library(force: bool = False, verbose: bool = True) -> str:
         if verbose:
             print(f"[domain-rag_amd] compiling {len(jobs)} HIP source(s) for {ARCH} ...", file=sys.stderr)
         try:
-            with ThreadPoolExecutor(max_workers=min(8, len(jobs))) as ex:
+            workers = int(os.environ.get("MAX_JOBS") or 8)
+            with ThreadPoolExecutor(max_workers=max(1, min(workers, 16, len(jobs)))) as ex:
                 list(ex.map(compile_one, jobs))
         except Exception:
             # a library linked from an earlier state of the sources must not outlive a failed build of the current one

@@ -1,4 +1,4 @@
-"""Generator of the hand-placed K loop of gemm_bf16_w4 (csrc/gemm_bf16.hip): the 256 x 256 x 64 tile as FOUR waves x (128 x 128), one wave per
+"""Generator of the hand-placed K loop of gemm_bf16_w4 (csrc/gemm_bf16_w4p.hip): the 256 x 256 x 64 tile as FOUR waves x (128 x 128), one wave per
 SIMD with the whole 512-entry register file — a third less LDS -> register traffic per flop than the 8-wave kernel (the vendor library's
 MT256x256x64 kernel on this chip has the same shape: 256 threads, 130 KiB of LDS; profiles/r05_yardstick.log).
 

@@ -16,7 +16,7 @@ rows = {}
 for k in f:
     n, fk, ns = f[k]
     wk = w.get(k, (0, 0.0, 0))[1]
-    dma = "_GLOBAL__N_1" in k and "at6native" not in k      # this repo's kernels: all loads are 16 B/lane (wide, coalesced)
+    dma = ("_GLOBAL__N_1" in k or "drag_gemm" in k) and "at6native" not in k      # this repo's kernels (anonymous namespace; the GEMMs: drag_gemm): all loads are 16 B/lane (wide, coalesced)
     fetch_bytes = fk * 1024 * (2 if dma else 1)
     rows[k] = {"launches": n, "fetch_bytes_per_launch": fetch_bytes / n, "write_bytes_per_launch": wk * 1024 / n,
                "hbm_bytes_per_launch": (fetch_bytes + wk * 1024) / n, "avg_us": ns / n / 1e3, "fetch_x2_correction": dma}

@@ -1,6 +1,6 @@
 """The kernels that issue LDS reads from inline asm (attention_q64_kernel, gemm_bf16_deep) rely on one rule: nothing but asm statements sits
 between a read and the s_waitcnt that retires it, because hipcc takes the destination for defined as soon as the statement ends and may copy
-it.  scripts/check_asm_loads.py compiles the two sources to gfx950 assembly (no GPU needed, about a minute) and walks every such kernel for an
+it.  scripts/check_asm_loads.py compiles the checked sources to gfx950 assembly (no GPU needed, about a minute) and walks every such kernel for an
 instruction that touches the destination of an outstanding read."""
 import os
 import shutil

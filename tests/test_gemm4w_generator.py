@@ -97,7 +97,7 @@ def test_every_register_the_product_stream_writes_is_an_output_or_a_clobber():
     text = open(HEADER).read()
     clob = set(re.findall(r'"(\w+)"', re.search(r"#define G4W_CLOBBERS (.*)", text).group(1)))
     assert "m0" in clob and {f"v{i}" for i in range(128)} <= clob
-    src = open(os.path.join(ROOT, "domain-rag_amd", "csrc", "gemm_bf16.hip")).read()
+    src = open(os.path.join(ROOT, "domain-rag_amd", "csrc", "gemm_bf16_w4p.hip")).read()
     for stmt in re.findall(r"asm volatile\((G4W_D_STAGE0_NOWAIT|G4W_P_FIRST G4W_P_PAIR0 G4W_P_LOOP G4W_P_TAIL)(.*?)\);", src, re.S):
         assert '"m0"' in stmt[1] or "G4W_CLOBBERS" in stmt[1], stmt[0]
     written = set()

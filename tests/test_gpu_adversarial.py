@@ -260,7 +260,7 @@ def test_gemm_w4p_forced_outlier_channels(gpu, M, factor):
         out_act = ops.gemm(a.to(gpu), w.to(gpu), bias=bias.to(gpu), act=ops.ACT_GELU_TANH)
     _gemm_check(out, a, w, bias=bias, what=f"w4p forced, outliers x{factor:g}, M {M}")
     # GELU(tanh) as torch applies it to a bf16 Linear's output (the reference's F.gelu(linear(x))): the pre-activation is ROUNDED to bf16, the
-    # activation evaluated in float32 on that, the result rounded again (csrc/gemm_bf16.hip act4).  Against float64 of the exact pre-activation:
+    # activation evaluated in float32 on that, the result rounded again (csrc/gemm_bf16_kernels.h act4).  Against float64 of the exact pre-activation:
     # |gelu'| <= 1.13, so the first rounding (2^-8 |y|) and the accumulation error pass through at most amplified by that; then one output rounding.
     # (The first run of this test had the one-rounding bar and failed at 1.9 x it in the linear region, where |y| = |gelu(y)|: the bar was wrong.)
     y = a.double() @ w.double().T + bias.double()

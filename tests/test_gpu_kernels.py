@@ -876,7 +876,7 @@ def test_gemm_kernels_are_bit_identical(gpu, M, N, K):
         outs.append(y)
         return [o.cpu() for o in outs]
 
-    codes = [1, 42, 43, 22, 23, 24, 13, 14, 113, 123, 133, 143, 0] + ([2, 3] if N >= 256 and K >= 256 else [])      # 1xx: 192-column tiles; 3: the 4-wave persistent kernel (where K % 128 == 0, else the 8-wave one)
+    codes = [1, 42, 43, 32, 33, 22, 23, 24, 13, 14, 113, 123, 133, 143, 132, 142, 134, 144, 0] + ([2, 3] if N >= 256 and K >= 256 else [])      # 1xx: 192-column tiles; 3: the 4-wave persistent kernel (where K % 128 == 0, else the 8-wave one)
     res = {}
     for code in codes:
         with ops.options(gemm_kernel=code):
@@ -890,7 +890,7 @@ def test_gemm_kernels_are_bit_identical(gpu, M, N, K):
 
 @pytest.mark.parametrize("M,N,K,rpb", [(2560, 1024, 256, 1280), (2304, 1100, 320, 2304), (5337 * 2, 768, 256, 5337), (4100, 3072, 512, 4100), (1536, 512, 256, 512)])
 def test_specialised_epilogue_equals_the_general_one(gpu, M, N, K, rpb):
-    """round 4: interior tiles inside one batch take a specialised, branch-free epilogue (csrc/gemm_bf16.hip staged_rows_fast: plain / bias,
+    """round 4: interior tiles inside one batch take a specialised, branch-free epilogue (csrc/gemm_bf16_kernels.h staged_rows_fast: plain / bias,
     bias + activation on every column, residual, gate + residual); "gemm_epilogue" = 1 sends every tile through the general one.  Same
     arithmetic operation for operation: the outputs must be identical for every kernel family, with tiles that cross a batch of the row
     map (rpb not a multiple of the tile), ragged edges, activation starting inside the matrix (act_n0) and with no bias at all"""
