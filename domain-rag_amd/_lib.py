@@ -121,6 +121,8 @@ SIGNATURES = {
     "drag_jpeg_decode_rgb": (c_int, [c_void_p] * 4 + [c_int, c_int64, c_int64, c_void_p, c_int64] + [c_void_p] * 5),
     "drag_png_plan": (c_int, [c_int] * 4 + [c_void_p, c_void_p]),
     "drag_png_encode": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "drag_jpeg_encode_plan": (c_int, [c_int] * 5 + [c_void_p, c_void_p]),
+    "drag_jpeg_encode": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -19,6 +19,12 @@ from datetime import datetime
 
 from .. import hostlogic as H
 
+JPEG_SUFFIXES = (".jpg", ".jpeg", ".jpe", ".jfif")                # the names Pillow's `save(path)` writes as JPEG
+# --jpeg: who compresses a .jpg result.  Both routes write the same bytes (tests/test_gpu_stage0_jpeg.py).  Measured on an MI355X
+# (scripts/bench_stage0_jpeg.py, 16 frames of 504 x 376, two runs of 5 alternating passes; DESIGN.md kernel table): 11.49 / 11.52 ms per
+# image on the device route against 11.90 / 11.93 ms on the host route, every device pass below every host pass: the device route
+JPEG_DEFAULT = "gpu"
+
 
 def setup_logger():
     log_dir = "../lamainpaint/logs"
@@ -46,6 +52,8 @@ def build_parser():
     p.add_argument("--lama-model", type=str, default=None, help="big-lama.pt (default: $LAMA_MODEL or ./model/big-lama.pt)")
     p.add_argument("--synthetic-weights", action="store_true")
     p.add_argument("--tiny", action="store_true", help="test hook: tiny generator")
+    p.add_argument("--jpeg", choices=["gpu", "host"], default=JPEG_DEFAULT,
+                   help="gpu: .jpg results stay on the device and are compressed there (jpeg.encode: Pillow's bytes); host: Pillow's Image.save")
     return p
 
 
@@ -61,21 +69,63 @@ def _annotation_index(annotation_file):
     return info_of, anns_of, names, len(data.get("annotations", []))
 
 
-def _inpaint_one(simple_lama, image_path, info, boxes):
-    """one image of the loop (:159-215): RGB, annotated size (PIL's default bicubic resize if the file differs), union mask"""
+def _open_rgb(image_path, size):
+    """the image as the loop reads it (:159-170): RGB, at the annotated size (PIL's default bicubic resize if the file differs)"""
     from PIL import Image
     image = Image.open(image_path)
     if image.mode != "RGB":
         image = image.convert("RGB")
-    size = (info["width"], info["height"])
     if image.size != size:
         image = image.resize(size)
+    return image
+
+
+def _inpaint_one(simple_lama, image_path, info, boxes):
+    """one image of the loop (:159-215): RGB, annotated size, union mask"""
+    from PIL import Image
+    size = (info["width"], info["height"])
     mask = Image.fromarray(H.inpaint_mask_array(size[0], size[1], boxes), mode="L")
-    return simple_lama(image, mask)
+    return simple_lama(_open_rgb(image_path, size), mask)
 
 
-def process_dataset(dataset_name, shot_count, logger, simple_lama, rank: int = 0, world: int = 1):
-    """process_dataset (:78-224) -> (processed, errors).  ``simple_lama`` is the model object: (PIL RGB, PIL L) -> PIL."""
+def _inpaint_one_on_device(simple_lama, image_path, info, boxes):
+    """``_inpaint_one`` for the HIP model without the trip of the RESULT through the host: -> the uint8 frame on the device.  The
+    source is read by PIL as on the host route and uploaded: measured, that takes 0.58 ms per 504 x 376 file, against 19.7 ms for
+    ``jpeg.decode_files`` on one file and 1.2 ms per file in a batch of 64 (its entropy stage runs one file per lane)."""
+    import numpy as np
+    import torch
+    size = (info["width"], info["height"])
+    image_dev = torch.from_numpy(np.array(_open_rgb(image_path, size))).to(simple_lama.device)
+    mask_dev = torch.from_numpy(H.inpaint_mask_array(size[0], size[1], boxes)).to(simple_lama.device)
+    return simple_lama.model(image_dev, mask_dev)
+
+
+def _save_frame(frame, out_name, logger):
+    """a device frame -> ``out_name`` (a JPEG name): compressed on the device; if the encoder raises, Pillow writes the file
+    (the same bytes).  -> who wrote it: "device" | "PIL" """
+    from .. import jpeg
+    try:
+        data = jpeg.encode(frame)[0]
+    except Exception as e:
+        logger.warning(f"GPU JPEG 编码失败 ({e}), 改用 Pillow: {out_name}")
+        from PIL import Image
+        Image.fromarray(frame.cpu().numpy()).save(out_name)
+        return "PIL"
+    with open(out_name, "wb") as f:
+        f.write(data)
+    return "device"
+
+
+def process_dataset(dataset_name, shot_count, logger, simple_lama, rank: int = 0, world: int = 1, jpeg: str = JPEG_DEFAULT):
+    """process_dataset (:78-224) -> (processed, errors).  ``simple_lama`` is the model object: (PIL RGB, PIL L) -> PIL.
+    ``jpeg``: "gpu" keeps a .jpg result of the HIP ``SimpleLama`` on the device up to the finished file's bytes; "host", any other
+    model object and any other file type go through PIL."""
+    if jpeg not in ("gpu", "host"):
+        raise ValueError(f"process_dataset: jpeg must be 'gpu' or 'host', got {jpeg!r}")
+    on_device = False
+    if jpeg == "gpu":
+        from ..lama import SimpleLama
+        on_device = isinstance(simple_lama, SimpleLama)
     logger.info(f"数据集 {dataset_name} / {shot_count}-shot: 开始")
     dataset_path = os.path.join("../datasets", dataset_name)
     train_images_dir = os.path.join(dataset_path, "train")
@@ -108,10 +158,17 @@ def process_dataset(dataset_name, shot_count, logger, simple_lama, rank: int = 0
             cats = ", ".join("{}(ID:{})".format(names.get(a["category_id"], "未知类别 {}".format(a["category_id"])), a["category_id"]) for a in anns)
             logger.info(f"多bbox图像 {info['file_name']}: {len(anns)} 个bbox, 类别: {cats}")
         try:
-            result = _inpaint_one(simple_lama, image_path, info, [a["bbox"] for a in anns])
             out_name = os.path.join(output_dir, info["file_name"])
-            os.makedirs(os.path.dirname(out_name), exist_ok=True)
-            result.save(out_name)
+            boxes = [a["bbox"] for a in anns]
+            if on_device and out_name.lower().endswith(JPEG_SUFFIXES):
+                frame = _inpaint_one_on_device(simple_lama, image_path, info, boxes)
+                os.makedirs(os.path.dirname(out_name), exist_ok=True)
+                writer = _save_frame(frame, out_name, logger)
+                logger.info(f"设备路径 {info['file_name']}: JPEG 写入 {writer}")
+            else:
+                result = _inpaint_one(simple_lama, image_path, info, boxes)
+                os.makedirs(os.path.dirname(out_name), exist_ok=True)
+                result.save(out_name)
             done += 1
         except Exception as e:                                     # reference convention: log, count, continue
             logger.error(f"图像 {image_path} 处理失败: {e}")
@@ -140,7 +197,7 @@ def main(argv=None):
     for ds in args.datasets:
         for shot in args.shots:
             try:
-                for i, v in enumerate(process_dataset(ds, shot, logger, simple_lama, rank, world)):
+                for i, v in enumerate(process_dataset(ds, shot, logger, simple_lama, rank, world, jpeg=args.jpeg)):
                     totals[i] += v
             except Exception as e:
                 logger.error(f"数据集 {ds} / {shot}-shot 中断: {e}")

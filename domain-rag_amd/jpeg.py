@@ -10,6 +10,12 @@ PIL (same bytes by definition).
     batch = decode_files([bytes, ...], device)      # -> DecodedBatch
     batch.image(i)                                   # uint8 [H, W, 3] view on the device, or None if status[i] != 0
     for (h, w), idx, imgs in batch.groups():         # same-size images as one dense [m, h, w, 3] tensor (for the resample kernel)
+
+and pixels on the GPU -> JPEG files (``drag_jpeg_encode``), byte-identical to ``Image.save(path)`` / ``Image.save(f, "JPEG",
+quality=q, subsampling=s)`` — the writer of the reference's stage-0 frames (lama_inpaint/lama_inpaint.py:211), whose files stages 1
+and 2 read back:
+
+    files = encode(images, quality=75, subsampling=2)   # uint8 [n, H, W, 3] / [H, W, 3] / [n, H, W, 1] / [H, W, 1] -> list of bytes
 """
 from __future__ import annotations
 
@@ -236,3 +242,53 @@ def info_dict(row: np.ndarray) -> dict:
     return dict(status=r[0], width=r[1], height=r[2], ncomp=r[3], hs=r[4:7], vs=r[7:10], tq=r[10:13], td=r[13:16], ta=r[16:19],
                 hmax=r[19], vmax=r[20], mcus_x=r[21], mcus_y=r[22], restart_interval=r[23], scan_off=r[24], dqt_off=r[25:29],
                 dqt_16=r[29:33], dht_off=r[33:41], progressive=r[41], cid=r[42:45])
+
+
+_enc_scratch: dict = {}
+
+
+def _enc_buffers(device, ws_bytes: int, out_bytes: int):
+    """scratch + output buffers of the encoder, reused per device and grown geometrically (a stage writes same-size frames)"""
+    key = str(device)
+    ws, out = _enc_scratch.get(key, (None, None))
+    if ws is None or ws.numel() < ws_bytes:
+        ws = torch.empty(max(ws_bytes, 2 * (ws.numel() if ws is not None else 0)), dtype=torch.uint8, device=device)
+    if out is None or out.numel() < out_bytes:
+        out = torch.empty(max(out_bytes, 2 * (out.numel() if out is not None else 0)), dtype=torch.uint8, device=device)
+    _enc_scratch[key] = (ws, out)
+    return ws, out
+
+
+def encode(images: torch.Tensor, quality: int = 75, subsampling: int = 2) -> list:
+    """``images``: uint8, on the GPU: ``[n, H, W, 3]`` / ``[H, W, 3]`` (RGB files) or ``[n, H, W, 1]`` / ``[H, W, 1]`` (grey files);
+    a view that is not dense is copied first.  ``quality`` 1..100 and ``subsampling`` 0 / 1 / 2 (4:4:4 / 4:2:2 / 4:2:0; ignored
+    for grey) are Pillow's; the defaults are what ``Image.save(path)`` uses.  Returns one ``bytes`` object (a whole .jpg file, the
+    bytes Pillow writes for the same pixels) per image.  ``optimize``, ``progressive`` and restart markers are not offered."""
+    lib = _lib.load()
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8:
+        raise ValueError("jpeg.encode: a uint8 tensor is expected")
+    if images.device.type != "cuda":
+        raise RuntimeError("jpeg.encode: the JPEG encoder is a GPU path (domain-rag_amd has no CPU fallback)")
+    if images.dim() == 3:
+        images = images[None]
+    if images.dim() != 4 or images.shape[-1] not in (1, 3):
+        raise ValueError(f"jpeg.encode: [n, H, W, 3], [H, W, 3], [n, H, W, 1] or [H, W, 1] expected, got {tuple(images.shape)}")
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError(f"jpeg.encode: quality must be an integer 1..100, got {quality!r}")
+    if isinstance(subsampling, bool) or subsampling not in (0, 1, 2):
+        raise ValueError(f"jpeg.encode: subsampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0), got {subsampling!r}")
+    images = images.contiguous()
+    n, H, W, C = (int(v) for v in images.shape)
+    if n == 0:
+        return []
+    if H < 1 or W < 1 or H > 65535 or W > 65535 or H * W > 1 << 24:
+        raise ValueError(f"jpeg.encode: 1 <= H, W <= 65535 and H * W <= 2^24 expected, got {H} x {W}")
+    ws_bytes, stride = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(lib.drag_jpeg_encode_plan(n, H, W, C, subsampling, ctypes.byref(ws_bytes), ctypes.byref(stride)), "drag_jpeg_encode_plan")
+    ws, out = _enc_buffers(images.device, ws_bytes.value + 256, n * stride.value)
+    pad = (-ws.data_ptr()) % 256
+    sizes = torch.empty(n, dtype=torch.int64, device=images.device)
+    check(lib.drag_jpeg_encode(_p(images), n, H, W, C, quality, subsampling, ws.data_ptr() + pad, ws.numel() - pad, _p(out), stride.value,
+                               _p(sizes), _stream()), "drag_jpeg_encode")
+    host_sizes = sizes.cpu().tolist()                      # the one synchronisation
+    return [out[i * stride.value: i * stride.value + sz].cpu().numpy().tobytes() for i, sz in enumerate(host_sizes)]

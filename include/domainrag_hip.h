@@ -487,6 +487,22 @@ int drag_png_plan(int32_t n, int32_t H, int32_t W, int32_t C, int64_t* workspace
 int drag_png_encode(const void* images, int32_t n, int32_t H, int32_t W, int32_t C, void* workspace, int64_t workspace_bytes,
                     void* out, int64_t out_stride, int64_t* sizes, void* stream);
 
+/* uint8 images in HBM -> complete baseline JPEG files in HBM, BYTE-IDENTICAL to what Pillow writes for `Image.save(path)` /
+ * `Image.save(f, "JPEG", quality=q, subsampling=s)` (libjpeg's default path: fixed-point RGB -> YCbCr, box downsampling, ISLOW
+ * forward DCT, Annex K quantisation tables scaled by the quality, Annex K Huffman tables, one interleaved scan, JFIF header);
+ * replaces the host-side `result.save(output_filename)` of the reference's stage-0 frames (lama_inpaint/lama_inpaint.py:211),
+ * whose .jpg files are the inputs of stages 1 and 2.  All on the device, stream-ordered, no host round trip.
+ *   drag_jpeg_encode_plan: sizes for a batch of n dense images [H, W, C] (C = 3 RGB, 1 grey; 1 <= W, H <= 65535 and
+ *                          W * H <= 2^24 as for the decoder): *workspace_bytes of scratch, *out_stride bytes per image in the
+ *                          output buffer (worst case: 256 stream bytes per 8x8 block, every one of them stuffed).
+ *   drag_jpeg_encode:      images uint8 [n, H, W, C] -> file i at out + i * out_stride, its length in sizes[i] (device int64);
+ *                          quality 1..100; subsampling 0 / 1 / 2 = 4:4:4 / 4:2:2 / 4:2:0 (Pillow's numbers; ignored for grey);
+ *                          workspace 256-byte aligned.  No optimised tables, progressive scans or restart markers. */
+int drag_jpeg_encode_plan(int32_t n, int32_t H, int32_t W, int32_t C, int32_t subsampling, int64_t* workspace_bytes,
+                          int64_t* out_stride);
+int drag_jpeg_encode(const void* images, int32_t n, int32_t H, int32_t W, int32_t C, int32_t quality, int32_t subsampling,
+                     void* workspace, int64_t workspace_bytes, void* out, int64_t out_stride, int64_t* sizes, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Prompt encoders (T5-XXL encoder, CLIP-L text tower; reached from pipe_prior_redux(...) at batch_generate_flux_kshot.py:459-465 /
  * outpainting_updown_sampling_redux.py:1237-1243 on a prompt-cache miss).  Every Linear is drag_gemm_bf16; these are the rest.
