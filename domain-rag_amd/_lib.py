@@ -119,6 +119,10 @@ SIGNATURES = {
     "drag_read_files": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int]),
     "drag_jpeg_parse": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "drag_jpeg_decode_rgb": (c_int, [c_void_p] * 4 + [c_int, c_int64, c_int64, c_void_p, c_int64] + [c_void_p] * 5),
+    "drag_jpeg_par_geometry": (c_int, [c_void_p] * 3),
+    "drag_jpeg_par_plan": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 3),
+    "drag_jpeg_decode_rgb_par": (c_int, [c_void_p] * 4 + [c_int, c_int64, c_int64, c_void_p, c_int64] + [c_void_p] * 4
+                                 + [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "drag_png_plan": (c_int, [c_int] * 4 + [c_void_p, c_void_p]),
     "drag_png_encode": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "drag_jpeg_encode_plan": (c_int, [c_int] * 5 + [c_void_p, c_void_p]),

@@ -24,6 +24,10 @@ JPEG_SUFFIXES = (".jpg", ".jpeg", ".jpe", ".jfif")                # the names Pi
 # (scripts/bench_stage0_jpeg.py, 16 frames of 504 x 376, two runs of 5 alternating passes; DESIGN.md kernel table): 11.49 / 11.52 ms per
 # image on the device route against 11.90 / 11.93 ms on the host route, every device pass below every host pass: the device route
 JPEG_DEFAULT = "gpu"
+# --source: who decodes a .jpg source.  Both routes hand the model the same pixels (tests/test_gpu_stage0_source.py).  "host" until a
+# measurement says otherwise; the rule is --jpeg's: "gpu" only if its per-image wall clock is not above "host"'s in the same run
+# (scripts/bench_stage0_jpeg.py --source gpu).
+SOURCE_DEFAULT = "host"
 
 
 def setup_logger():
@@ -54,6 +58,9 @@ def build_parser():
     p.add_argument("--tiny", action="store_true", help="test hook: tiny generator")
     p.add_argument("--jpeg", choices=["gpu", "host"], default=JPEG_DEFAULT,
                    help="gpu: .jpg results stay on the device and are compressed there (jpeg.encode: Pillow's bytes); host: Pillow's Image.save")
+    p.add_argument("--source", choices=["gpu", "host"], default=SOURCE_DEFAULT,
+                   help="gpu: a .jpg source the device parser accepts at the annotated size is decoded on the device "
+                        "(jpeg.decode_files(entropy='parallel'): Pillow's bytes); host: Pillow's Image.open")
     return p
 
 
@@ -88,14 +95,35 @@ def _inpaint_one(simple_lama, image_path, info, boxes):
     return simple_lama(_open_rgb(image_path, size), mask)
 
 
-def _inpaint_one_on_device(simple_lama, image_path, info, boxes):
-    """``_inpaint_one`` for the HIP model without the trip of the RESULT through the host: -> the uint8 frame on the device.  The
-    source is read by PIL as on the host route and uploaded: measured, that takes 0.58 ms per 504 x 376 file, against 19.7 ms for
-    ``jpeg.decode_files`` on one file and 1.2 ms per file in a batch of 64 (its entropy stage runs one file per lane)."""
+def _decode_source_on_device(simple_lama, image_path, size, logger):
+    """``--source gpu``: the file -> uint8 [H, W, 3] on the device through ``jpeg.stage_paths`` / ``decode_files(entropy="parallel")``
+    (Pillow's bytes: tests/test_gpu_jpeg_parallel.py), or None when the caller has to read it with ``_open_rgb``: a file the device
+    parser does not accept (CMYK, arithmetic coding, ...: status != 0, or entropy data that does not end at EOI), a size that differs
+    from the annotation (PIL resizes those), a file that cannot be read (``_open_rgb`` raises the error the loop logs), and any
+    exception of the device route (logged)."""
+    from .. import jpeg
+    try:
+        staged = jpeg.stage_paths([image_path], simple_lama.device)
+        if staged.errors:
+            return None
+        batch = jpeg.decode_files(staged, simple_lama.device, entropy="parallel")
+        if int(batch.status[0]) != 0 or (int(batch.width[0]), int(batch.height[0])) != tuple(size):
+            return None
+        return batch.image(0)
+    except Exception as e:
+        logger.warning(f"GPU JPEG 解码失败 ({e}), 改用 Pillow: {image_path}")
+        return None
+
+
+def _inpaint_one_on_device(simple_lama, image_path, info, boxes, image_dev=None):
+    """``_inpaint_one`` for the HIP model without the trip of the RESULT through the host: -> the uint8 frame on the device.
+    ``image_dev``: the source already on the device (``_decode_source_on_device``); without it the source is read by PIL as on the
+    host route and uploaded (measurements of both: DESIGN.md (f), scripts/bench_jpeg_decode_single.py)."""
     import numpy as np
     import torch
     size = (info["width"], info["height"])
-    image_dev = torch.from_numpy(np.array(_open_rgb(image_path, size))).to(simple_lama.device)
+    if image_dev is None:
+        image_dev = torch.from_numpy(np.array(_open_rgb(image_path, size))).to(simple_lama.device)
     mask_dev = torch.from_numpy(H.inpaint_mask_array(size[0], size[1], boxes)).to(simple_lama.device)
     return simple_lama.model(image_dev, mask_dev)
 
@@ -116,16 +144,22 @@ def _save_frame(frame, out_name, logger):
     return "device"
 
 
-def process_dataset(dataset_name, shot_count, logger, simple_lama, rank: int = 0, world: int = 1, jpeg: str = JPEG_DEFAULT):
+def process_dataset(dataset_name, shot_count, logger, simple_lama, rank: int = 0, world: int = 1, jpeg: str = JPEG_DEFAULT,
+                    source: str = SOURCE_DEFAULT):
     """process_dataset (:78-224) -> (processed, errors).  ``simple_lama`` is the model object: (PIL RGB, PIL L) -> PIL.
     ``jpeg``: "gpu" keeps a .jpg result of the HIP ``SimpleLama`` on the device up to the finished file's bytes; "host", any other
-    model object and any other file type go through PIL."""
+    model object and any other file type go through PIL.  ``source``: "gpu" decodes a .jpg source of the HIP ``SimpleLama`` on the
+    device (``_decode_source_on_device`` says which files); "host", any other model object and every other file are opened by PIL.
+    Both settings of both switches write the same files."""
     if jpeg not in ("gpu", "host"):
         raise ValueError(f"process_dataset: jpeg must be 'gpu' or 'host', got {jpeg!r}")
-    on_device = False
-    if jpeg == "gpu":
+    if source not in ("gpu", "host"):
+        raise ValueError(f"process_dataset: source must be 'gpu' or 'host', got {source!r}")
+    on_device = source_on_device = False
+    if jpeg == "gpu" or source == "gpu":
         from ..lama import SimpleLama
-        on_device = isinstance(simple_lama, SimpleLama)
+        on_device = jpeg == "gpu" and isinstance(simple_lama, SimpleLama)
+        source_on_device = source == "gpu" and isinstance(simple_lama, SimpleLama)
     logger.info(f"数据集 {dataset_name} / {shot_count}-shot: 开始")
     dataset_path = os.path.join("../datasets", dataset_name)
     train_images_dir = os.path.join(dataset_path, "train")
@@ -160,11 +194,21 @@ def process_dataset(dataset_name, shot_count, logger, simple_lama, rank: int = 0
         try:
             out_name = os.path.join(output_dir, info["file_name"])
             boxes = [a["bbox"] for a in anns]
-            if on_device and out_name.lower().endswith(JPEG_SUFFIXES):
-                frame = _inpaint_one_on_device(simple_lama, image_path, info, boxes)
+            image_dev = None
+            if source_on_device and image_path.lower().endswith(JPEG_SUFFIXES):
+                image_dev = _decode_source_on_device(simple_lama, image_path, (info["width"], info["height"]), logger)
+                if image_dev is not None:
+                    logger.info(f"设备读取 {info['file_name']}: JPEG 解码于 device")
+            device_out = on_device and out_name.lower().endswith(JPEG_SUFFIXES)
+            if device_out or image_dev is not None:
+                frame = _inpaint_one_on_device(simple_lama, image_path, info, boxes, image_dev)
                 os.makedirs(os.path.dirname(out_name), exist_ok=True)
-                writer = _save_frame(frame, out_name, logger)
-                logger.info(f"设备路径 {info['file_name']}: JPEG 写入 {writer}")
+                if device_out:
+                    writer = _save_frame(frame, out_name, logger)
+                    logger.info(f"设备路径 {info['file_name']}: JPEG 写入 {writer}")
+                else:                                              # what SimpleLama.__call__ hands back, saved as on the host route
+                    from PIL import Image
+                    Image.fromarray(frame.cpu().numpy()).save(out_name)
             else:
                 result = _inpaint_one(simple_lama, image_path, info, boxes)
                 os.makedirs(os.path.dirname(out_name), exist_ok=True)
@@ -197,7 +241,7 @@ def main(argv=None):
     for ds in args.datasets:
         for shot in args.shots:
             try:
-                for i, v in enumerate(process_dataset(ds, shot, logger, simple_lama, rank, world, jpeg=args.jpeg)):
+                for i, v in enumerate(process_dataset(ds, shot, logger, simple_lama, rank, world, jpeg=args.jpeg, source=args.source)):
                     totals[i] += v
             except Exception as e:
                 logger.error(f"数据集 {ds} / {shot}-shot 中断: {e}")

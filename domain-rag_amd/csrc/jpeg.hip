@@ -20,6 +20,7 @@
 // The last two are plain data-parallel integer kernels bound by the load/store units (no reuse to stage in LDS).
 #include "drag_common.h"
 #include "jpeg_core.h"
+#include "jpeg_internal.h"
 
 namespace {
 
@@ -37,19 +38,6 @@ struct LdsTable {
 };
 typedef LdsTable<6, 16> DcTable;
 typedef LdsTable<6, 256> AcTable;      // 6-bit direct tables keep the wave at 85 KiB of LDS: see JPEG_HUFF_LDS
-
-struct JpegArgs {
-  const uint8_t* data;
-  const int64_t* off;       // [n + 1] byte offsets of the files inside `data`
-  const JpegInfo* info;     // [n]
-  const int64_t* plan;      // [n, 3]: coefficient offset (int16 elements), plane offset (bytes), output offset (bytes)
-  int16_t* coef;
-  uint8_t* planes;
-  uint16_t* qtab;           // [n, 3, 64] quantisation tables in natural order
-  uint8_t* out;
-  int32_t* scan_status;     // [n]: 0 = the entropy-coded data ended at the EOI marker, as a clean file's does
-  int n;
-};
 
 __global__ __launch_bounds__(64) void jpeg_parse_kernel(const uint8_t* data, const int64_t* off, int n, JpegInfo* info) {
   // the descriptor is indexed dynamically while it is built (component / table numbers come from the file), so a per-lane local
@@ -107,6 +95,7 @@ __global__ __launch_bounds__(64) void jpeg_huffman_kernel(JpegArgs a) {
   for (int k = lane; k < 80; k += 64) nat[k] = (uint8_t)jpeg_natural_order(k);
   __syncthreads();
   if (i >= a.n) return;
+  if (a.mask && a.mask[i] == 0) return;              // the parallel entropy route (jpeg_par.hip) has decoded this file
   const JpegInfo& o = a.info[i];
   if (o.status != 0) { a.scan_status[i] = 0; return; }
   if (o.progressive) return;                         // jpeg_progressive_kernel's file
@@ -288,8 +277,16 @@ extern "C" int drag_jpeg_decode_rgb(const void* data, const int64_t* offsets, co
   JpegArgs a;
   a.data = (const uint8_t*)data; a.off = offsets; a.info = (const JpegInfo*)info; a.plan = plan;
   a.coef = (int16_t*)coef_ws; a.planes = (uint8_t*)plane_ws; a.qtab = (uint16_t*)qtab_ws; a.out = (uint8_t*)out_rgb; a.scan_status = scan_status; a.n = n;
+  a.mask = nullptr;                                                       // every file goes to the lane kernel
   hipError_t e = hipMemsetAsync(coef_ws, 0, (size_t)coef_bytes, st);     // blocks are sparse: only non-zero coefficients are stored
   DRAG_CHECK(e == hipSuccess, "drag_jpeg_decode_rgb: memset failed");
+  return jpeg_lane_and_pixels(a, max_blocks, max_pixels, st);
+}
+
+// the lane kernels (sequential files the mask names — all of them without a mask — and progressive files), then IDCT and colour
+int jpeg_lane_and_pixels(const JpegArgs& a, int64_t max_blocks, int64_t max_pixels, hipStream_t st) {
+  const int n = a.n;
+  hipError_t e;
   const int lds = JPEG_HUFF_LDS;                                          // 85 KiB per wave
   static bool lds_ok = false;
   if (!lds_ok) {

@@ -34,8 +34,9 @@ STATUS_TEXT = {0: "ok", 1: "not a JPEG", 2: "truncated header", 3: "arithmetic /
 
 
 class DecodedBatch:
-    def __init__(self, info: np.ndarray, out: torch.Tensor, out_off: np.ndarray, order: np.ndarray):
+    def __init__(self, info: np.ndarray, out: torch.Tensor, out_off: np.ndarray, order: np.ndarray, par_stats=None):
         self.info = info                    # int32 [n, 48] (drag_jpeg_info words)
+        self.par_stats = par_stats          # entropy="parallel": int32 [n, 4] = route (0 lane, 1 parallel, 2 parallel then fallback), rounds, subsequences, fallback reason; else None
         self.status = info[:, 0].copy()
         self.width, self.height = info[:, 1].copy(), info[:, 2].copy()
         self._out, self._off, self._order = out, out_off, order
@@ -182,10 +183,25 @@ def _upload(blobs, device):
     return data, offsets
 
 
-def decode_files(blobs, device="cuda", check_scan: bool = True) -> DecodedBatch:
+def par_geometry() -> tuple:
+    """(bytes per subsequence, subsequences per workgroup span, cross-span round cap) of the parallel entropy route"""
+    lib = _lib.load()
+    g = (ctypes.c_int32 * 3)()
+    check(lib.drag_jpeg_par_geometry(ctypes.byref(g, 0), ctypes.byref(g, 4), ctypes.byref(g, 8)), "drag_jpeg_par_geometry")
+    return int(g[0]), int(g[1]), int(g[2])
+
+
+_par_scratch: dict = {}
+
+
+def decode_files(blobs, device="cuda", check_scan: bool = True, entropy: str = "lane") -> DecodedBatch:
     """``blobs``: list of bytes objects (whole files), or a ``StagedFiles`` (``stage_paths``).  All arithmetic runs in
     libdomainrag_hip.so.  ``check_scan``: read the per-file end-of-scan flags back (one more synchronisation) and mark files
-    whose entropy data does not end at EOI."""
+    whose entropy data does not end at EOI.  ``entropy``: ``"lane"`` = one file per lane (throughput is the batch size);
+    ``"parallel"`` = sequential-Huffman files are decoded by many lanes each (``drag_jpeg_decode_rgb_par``: the latency of ONE file;
+    same statuses and pixels for every input, ``DecodedBatch.par_stats`` says which route each file took)."""
+    if entropy not in ("lane", "parallel"):
+        raise ValueError(f"decode_files: entropy must be 'lane' or 'parallel', got {entropy!r}")
     lib = _lib.load()
     n = len(blobs)
     if n == 0:
@@ -223,17 +239,42 @@ def decode_files(blobs, device="cuda", check_scan: bool = True) -> DecodedBatch:
         oo += pixels[i] * 3
     out = torch.empty(max(oo, 1), dtype=torch.uint8, device=device)
     if not ok.any():
-        return DecodedBatch(info, out, plan[:, 2], order)
+        return DecodedBatch(info, out, plan[:, 2], order, np.zeros((n, 4), np.int32) if entropy == "parallel" else None)
     coef = torch.empty(max(co, 1), dtype=torch.int16, device=device)
     planes = torch.empty(max(po, 1), dtype=torch.uint8, device=device)
     qtab = torch.empty((n, 3, 64), dtype=torch.int16, device=device)
     d_plan = torch.from_numpy(plan).to(device)
     scan = torch.empty(n, dtype=torch.int32, device=device)
-    check(lib.drag_jpeg_decode_rgb(_p(data), _p(d_off), _p(d_info), _p(d_plan), n, int(blocks.max()), int(pixels.max()),
-                                   _p(coef), coef.numel() * 2, _p(planes), _p(qtab), _p(out), _p(scan), _stream()), "drag_jpeg_decode_rgb")
+    stats = None
+    if entropy == "parallel":
+        sizes = np.diff(np.asarray(offsets, dtype=np.int64))
+        scan_off = info[:, 24].astype(np.int64)
+        eligible = ok & (info[:, 41] == 0) & (sizes < (1 << 28)) & (scan_off > 0) & (scan_off < sizes)
+        scan_bytes = np.ascontiguousarray(np.where(eligible, sizes - scan_off, 0))
+        par_plan = np.empty((n, 2), dtype=np.int64)
+        totals = np.zeros(3, dtype=np.int64)
+        ws_bytes = ctypes.c_int64(0)
+        check(lib.drag_jpeg_par_plan(scan_bytes.ctypes.data, np.ascontiguousarray(blocks).ctypes.data, n, par_plan.ctypes.data,
+                                     totals.ctypes.data, ctypes.byref(ws_bytes)), "drag_jpeg_par_plan")
+        ws = _par_scratch.get(str(device))
+        if ws is None or ws.numel() < ws_bytes.value + 256:         # reused per device, grown geometrically
+            ws = torch.empty(max(ws_bytes.value + 256, 2 * (ws.numel() if ws is not None else 0)), dtype=torch.uint8, device=device)
+            _par_scratch[str(device)] = ws
+        pad = (-ws.data_ptr()) % 256
+        d_par = torch.from_numpy(par_plan).to(device)
+        stats = torch.empty((n, 4), dtype=torch.int32, device=device)
+        check(lib.drag_jpeg_decode_rgb_par(_p(data), _p(d_off), _p(d_info), _p(d_plan), n, int(blocks.max()), int(pixels.max()),
+                                           _p(coef), coef.numel() * 2, _p(planes), _p(qtab), _p(out), _p(scan), _p(d_par),
+                                           totals.ctypes.data, ws.data_ptr() + pad, ws.numel() - pad, _p(stats), _stream()),
+              "drag_jpeg_decode_rgb_par")
+    else:
+        check(lib.drag_jpeg_decode_rgb(_p(data), _p(d_off), _p(d_info), _p(d_plan), n, int(blocks.max()), int(pixels.max()),
+                                       _p(coef), coef.numel() * 2, _p(planes), _p(qtab), _p(out), _p(scan), _stream()), "drag_jpeg_decode_rgb")
     if check_scan:      # a scan that does not end at EOI: let libjpeg / PIL decide what the file means (status 10)
         info[:, 0] = np.where((info[:, 0] == 0) & (scan.cpu().numpy() != 0), 10, info[:, 0])
-    return DecodedBatch(info, out, plan[:, 2], order)
+    if stats is not None:
+        stats = stats.cpu().numpy()
+    return DecodedBatch(info, out, plan[:, 2], order, stats)
 
 
 def info_dict(row: np.ndarray) -> dict:

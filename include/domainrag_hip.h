@@ -466,6 +466,27 @@ int drag_jpeg_decode_rgb(const void* data, const int64_t* offsets, const drag_jp
                          int64_t max_blocks, int64_t max_pixels, void* coef_ws, int64_t coef_bytes, void* plane_ws,
                          void* qtab_ws, void* out_rgb, int32_t* scan_status, void* stream);
 
+/* The parallel entropy route for sequential-Huffman files (SOF0 / SOF1, one interleaved scan): ONE file is decoded by many lanes
+ * and, above 32 KiB of entropy data, by several workgroups (self-synchronising subsequences, propagated to the fixed point —
+ * csrc/jpeg_par_core.h); progressive files and every file the route cannot prove clean are decoded by drag_jpeg_decode_rgb's
+ * lane kernels inside the same call, so status, scan_status and pixels are drag_jpeg_decode_rgb's for every input.  Opt-in.
+ *   drag_jpeg_par_geometry: bytes per subsequence, subsequences per workgroup span, cap on the cross-span rounds.
+ *   drag_jpeg_par_plan (host only): scan_bytes[i] = file length - scan_off for a file of status 0 that is not progressive and
+ *     shorter than 2^28 bytes, 0 for any other; blocks[i] as for drag_jpeg_decode_rgb.  Writes par_plan int64 [n, 2] (first
+ *     subsequence, first span of file i in the workspace; -1 = lane route), totals int64 [3] (subsequences, spans, most spans
+ *     of one file) and the workspace size.
+ *   drag_jpeg_decode_rgb_par: drag_jpeg_decode_rgb's arguments, then par_plan (DEVICE copy), totals (host), the workspace
+ *     (device, 256-byte aligned) and stats int32 [n, 4] (device): route (0 lane: not eligible, 1 parallel, 2 parallel then
+ *     fallback to the lane kernel), cross-span rounds used, subsequences, fallback reason (0 none, 1 no code, 2 k past 63, 3 symbol
+ *     past the data, 4 RSTn without interval, 5 RSTn out of place, 6 block count, 7 end of data, 8 round cap). */
+int drag_jpeg_par_geometry(int32_t* subseq_bytes, int32_t* subseqs_per_workgroup, int32_t* round_cap);
+int drag_jpeg_par_plan(const int64_t* scan_bytes, const int64_t* blocks, int32_t n, int64_t* par_plan, int64_t* totals,
+                       int64_t* workspace_bytes);
+int drag_jpeg_decode_rgb_par(const void* data, const int64_t* offsets, const drag_jpeg_info* info, const int64_t* plan, int32_t n,
+                             int64_t max_blocks, int64_t max_pixels, void* coef_ws, int64_t coef_bytes, void* plane_ws,
+                             void* qtab_ws, void* out_rgb, int32_t* scan_status, const int64_t* par_plan, const int64_t* totals,
+                             void* workspace, int64_t workspace_bytes, int32_t* stats, void* stream);
+
 /* cv2.resize(img, (out_w, out_h)) (INTER_LINEAR, 8-bit path) of n differently sized RGB images + /255 -> f32 [n, 3, out_h, out_w]:
  * the input of the stem style vector (compute_resnet_features, retrieval/clip100_resnet_style_all_shots.py:186-196).  src: blob of
  * [h, w, 3] uint8 images at byte offsets src_off[n]; hw int32 [n, 2]; tab int32 [n, 8, L], L = max(out_h, out_w): per image the

@@ -3,8 +3,9 @@ dataset of same-size JPEG frames, big-lama architecture with seeded weights): th
 routes alternate in one process, pass after pass; the first pass of each is the warm-up and is not counted.  The files of the two
 routes are compared byte for byte.  A second JSON line times the steps of one image on their own (median of --reps, each ending in a
 device synchronise): reading the source (PIL + upload, what stage 0 does | jpeg.decode_files on one file and on all --images files at once, which stage 0 does not use: this is the record of why), the generator (device call | PIL in / PIL out), writing
-(device encode + write | copy back + Image.save).
-    python scripts/bench_stage0_jpeg.py [--size 504x376] [--images 16] [--passes 4] [--tiny]"""
+(device encode + write | copy back + Image.save).  With `--source gpu` a third route joins the alternating passes: `--jpeg gpu --source gpu`
+(the source decoded on the device by the parallel entropy route), compared with `--jpeg gpu --source host` under the same rule.
+    python scripts/bench_stage0_jpeg.py [--size 504x376] [--images 16] [--passes 4] [--tiny] [--source gpu]"""
 import argparse
 import json
 import logging
@@ -34,6 +35,7 @@ def main():
     ap.add_argument("--passes", type=int, default=4, help="timed passes per route (one more, the first, is the warm-up)")
     ap.add_argument("--reps", type=int, default=20, help="repeats per step of the breakdown")
     ap.add_argument("--tiny", action="store_true", help="tiny generator (rehearsal)")
+    ap.add_argument("--source", choices=["host", "gpu"], default="host", help="gpu: also time --jpeg gpu --source gpu in the alternating passes")
     args = ap.parse_args()
     ge.build()
     import torch
@@ -63,12 +65,15 @@ def main():
         logger = logging.getLogger("bench_stage0_jpeg"); logger.addHandler(logging.NullHandler()); logger.propagate = False
         model = SimpleLama()
         out_dir = os.path.join(root, "lamainpaint", ds, "1_shot")
-        times = {"host": [], "gpu": []}
+        routes = {"host": ("host", "host"), "gpu": ("gpu", "host")}              # name -> (--jpeg, --source)
+        if args.source == "gpu":
+            routes["gpu_source_gpu"] = ("gpu", "gpu")
+        times = {r: [] for r in routes}
         files = {}
         for p in range(args.passes + 1):
-            for route in ("host", "gpu"):
+            for route, (jpeg_route, source_route) in routes.items():
                 torch.cuda.synchronize(); t = time.perf_counter()
-                done, failed = s0.process_dataset(ds, "1", logger, model, jpeg=route)
+                done, failed = s0.process_dataset(ds, "1", logger, model, jpeg=jpeg_route, source=source_route)
                 torch.cuda.synchronize(); dt = time.perf_counter() - t
                 assert (done, failed) == (args.images, 0), (route, done, failed)
                 files[route] = {n: open(os.path.join(out_dir, n), "rb").read() for n in sorted(os.listdir(out_dir))}
@@ -104,6 +109,8 @@ def main():
         steps = {"read_pil_open_upload_ms": med(read_pil),
                  "read_device_decode_ms": med(lambda: jpeg.decode_files([data], dev).image(0)),
                  "read_device_decode_batch_ms_per_file": round(med(lambda: jpeg.decode_files(all_data, dev)) / len(all_data), 3),
+                 "read_device_decode_parallel_ms": med(lambda: jpeg.decode_files([data], dev, entropy="parallel").image(0)),
+                 "read_stage_paths_decode_parallel_ms": med(lambda: jpeg.decode_files(jpeg.stage_paths([src], dev), dev, entropy="parallel").image(0)),
                  "mask_build_upload_ms": med(lambda: torch.from_numpy(H.inpaint_mask_array(w, h, [anns[0]["bbox"]])).to(dev)),
                  "lama_device_in_device_out_ms": med(lambda: model.model(img_dev, mask_dev)),
                  "lama_pil_in_pil_out_ms": med(lambda: model(pil_img, pil_mask)),
@@ -111,10 +118,15 @@ def main():
                  "write_copy_back_pil_save_ms": med(lambda: Image.fromarray(frame.cpu().numpy()).save(tmp_out))}
         os.chdir("/")
     host, gpu = statistics.median(times["host"]), statistics.median(times["gpu"])
-    print(json.dumps({"size": f"{w}x{h}", "images": args.images, "passes": args.passes, "tiny": args.tiny, "identical": files["host"] == files["gpu"],
-                      "host_ms_per_image": round(host, 3), "gpu_ms_per_image": round(gpu, 3),
-                      "host_all": [round(v, 3) for v in times["host"]], "gpu_all": [round(v, 3) for v in times["gpu"]],
-                      "default_gpu_allowed": gpu <= host}), flush=True)
+    line = {"size": f"{w}x{h}", "images": args.images, "passes": args.passes, "tiny": args.tiny, "identical": all(f == files["host"] for f in files.values()),
+            "host_ms_per_image": round(host, 3), "gpu_ms_per_image": round(gpu, 3),
+            "host_all": [round(v, 3) for v in times["host"]], "gpu_all": [round(v, 3) for v in times["gpu"]],
+            "default_gpu_allowed": gpu <= host}
+    if "gpu_source_gpu" in times:                  # --source's rule is --jpeg's: gpu only if its wall clock is not above host's in the same run
+        sg = statistics.median(times["gpu_source_gpu"])
+        line.update({"source_gpu_ms_per_image": round(sg, 3), "source_gpu_all": [round(v, 3) for v in times["gpu_source_gpu"]],
+                     "source_default_gpu_allowed": sg <= gpu})
+    print(json.dumps(line), flush=True)
     print(json.dumps({"size": f"{w}x{h}", "reps": args.reps, "decode_batch": len(all_data), "source_file_kb": round(len(data) / 1e3, 1), **steps}), flush=True)
 
 
