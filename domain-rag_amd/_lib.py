@@ -25,6 +25,13 @@ class GemmArgs(ctypes.Structure):
     ]
 
 
+class GemmMxArgs(ctypes.Structure):
+    """mirror of ``drag_gemm_mx_args``"""
+    _fields_ = [(n, c_void_p) for n in ("Aq", "Ascale", "Wq", "Wscale", "C", "bias", "gate", "resid")] + \
+               [(n, c_int) for n in ("M", "N", "K", "ldc", "c_rows_per_batch")] + [("c_batch_stride", c_int64)] + \
+               [(n, c_int) for n in ("ldg", "act", "act_n0")]
+
+
 class ConvArgs(ctypes.Structure):
     """mirror of ``drag_conv_args``"""
     _fields_ = [("x", c_void_p), ("w", c_void_p), ("y", c_void_p), ("bias", c_void_p), ("resid", c_void_p)] + \
@@ -64,6 +71,8 @@ SIGNATURES = {
     "drag_gemm_set_workspace": (c_int, [c_void_p, c_int64]),
     "drag_gemm_bf16_splitk_slices": (c_int, [ctypes.POINTER(GemmArgs)]),
     "drag_gemm_bf16_pair_splitk_slices": (c_int, [ctypes.POINTER(GemmArgs), ctypes.POINTER(GemmArgs)]),
+    "drag_quantize_mxfp8": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "drag_gemm_mxfp8": (c_int, [ctypes.POINTER(GemmMxArgs), c_void_p]),
     "drag_qk_norm_rope_vt_bf16": (c_int, [c_void_p] * 8 + [c_int] * 5 + [c_float, c_void_p]),
     "drag_attention_bf16": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_int64, c_int, c_int64, c_float, c_void_p]),
     "drag_k_norm_rope_vt_bf16": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_float, c_void_p]),

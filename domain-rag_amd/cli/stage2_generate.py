@@ -42,6 +42,9 @@ def build_parser():
                    help="the reference's hard-coded coco_dataset_dir (batch_…:29)")
     p.add_argument("--synthetic-weights", action="store_true")
     p.add_argument("--tiny", action="store_true", help="test hook: tiny architectures, small images")
+    p.add_argument("--linear_precision", choices=["bf16", "mxfp8"], default=None,
+                   help="the DiT blocks' Linears: bf16, or OCP MXFP8 operands on the block-scaled matrix instruction (opt-in, lower "
+                        "precision); default: $DRAG_LINEAR_PRECISION, else bf16")
     p.add_argument("--text_encoder", choices=["transformers", "hip"], default="transformers",
                    help="what encodes a prompt without a prompt_cache file: the transformers T5 / CLIP modules (eager torch) or the HIP "
                         "encoders (domain_rag_amd.textenc); tokenizers are host Python either way")
@@ -274,7 +277,7 @@ def main(argv=None):
     from ..io_pool import ImageWriter
     args.writer = ImageWriter(args.io_workers)
     engine = Engine("dev", args.model_root, synthetic=args.synthetic_weights, tiny=args.tiny, device=torch.device("cuda", local),
-                    text_encoder=args.text_encoder)
+                    text_encoder=args.text_encoder, linear_precision=args.linear_precision)
     datasets = [args.dataset] if args.dataset else (DATASET_GROUPS[args.dataset_group] if args.dataset_group else list(results))
     tot_ok = tot_bad = 0
     for ds in datasets:

@@ -55,6 +55,9 @@ def build_parser():
     p.add_argument("--datasets_dir", type=str, default=DATASETS_DIR)
     p.add_argument("--synthetic-weights", action="store_true")
     p.add_argument("--tiny", action="store_true", help="test hook: tiny architectures, min_dimension 64")
+    p.add_argument("--linear_precision", choices=["bf16", "mxfp8"], default=None,
+                   help="the DiT blocks' Linears: bf16, or OCP MXFP8 operands on the block-scaled matrix instruction (opt-in, lower "
+                        "precision); default: $DRAG_LINEAR_PRECISION, else bf16")
     p.add_argument("--text_encoder", choices=["transformers", "hip"], default="transformers",
                    help="what encodes a prompt without a prompt_cache file: the transformers T5 / CLIP modules (eager torch) or the HIP "
                         "encoders (domain_rag_amd.textenc); tokenizers are host Python either way")
@@ -267,7 +270,7 @@ def run_rank(args, datasets, process_id, rank, world, gpu_process_id=None):
     local = int(os.environ.get("LOCAL_RANK", str(rank))) % max(torch.cuda.device_count(), 1)   # (more ranks than GPUs: share them)
     torch.cuda.set_device(local)
     engine = Engine("fill", args.model_root, synthetic=args.synthetic_weights, tiny=args.tiny, device=torch.device("cuda", local),
-                    text_encoder=args.text_encoder)
+                    text_encoder=args.text_encoder, linear_precision=args.linear_precision)
     rng = random.Random(None if args.seed is None else args.seed + rank)
     writer = ImageWriter(args.io_workers)
     done, failed = parse_resume_log(args.log_file) if (args.resume or args.failed_only) else (set(), set())

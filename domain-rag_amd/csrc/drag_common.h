@@ -124,7 +124,8 @@ __device__ __forceinline__ float wave_max(float v) {
   X(GEMM_NARROW, "gemm_narrow", 0, DRAG_OPT_PRODUCT)        \
   X(CONV_NO_SMALL_COUT, "conv_no_small_cout", 0, DRAG_OPT_PRODUCT) \
   X(CONV_NO_LIN, "conv_no_lin", 0, DRAG_OPT_PRODUCT)        \
-  X(CONV_TILE, "conv_tile", 0, DRAG_OPT_PRODUCT)
+  X(CONV_TILE, "conv_tile", 0, DRAG_OPT_PRODUCT)              \
+  X(GEMM_MX_KERNEL, "gemm_mx_kernel", 0, DRAG_OPT_PRODUCT)
 #define DRAG_OPT_ENUM(id, name, def, exp) DRAG_OPT_##id,
 enum { DRAG_OPTIONS(DRAG_OPT_ENUM) DRAG_OPT_COUNT };
 #undef DRAG_OPT_ENUM

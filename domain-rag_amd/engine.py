@@ -196,9 +196,10 @@ class Engine:
     """Everything stage 2 / stage 3 need, loaded once."""
 
     def __init__(self, kind: str, model_root: str = "./model", synthetic: bool = False, tiny: bool = False, device="cuda",
-                 seed: int = 0, text_encoder: str = "transformers"):
+                 seed: int = 0, text_encoder: str = "transformers", linear_precision: str | None = None):
         """``text_encoder``: what encodes a prompt-cache miss — "transformers" (the reference's modules, eager torch) or "hip"
-        (:mod:`.textenc`; with ``synthetic``: seeded encoders and stand-in tokenizers, results kept in memory)"""
+        (:mod:`.textenc`; with ``synthetic``: seeded encoders and stand-in tokenizers, results kept in memory).
+        ``linear_precision``: the DiT blocks' Linears, "bf16" or "mxfp8" (None: $DRAG_LINEAR_PRECISION, else bf16; :mod:`.flux`)"""
         assert kind in ("dev", "fill")
         if text_encoder not in ("transformers", "hip"):
             raise ValueError(f"text_encoder must be 'transformers' or 'hip', not {text_encoder!r}")
@@ -224,7 +225,7 @@ class Engine:
             vp = load_safetensors_dir(os.path.join(flux_dir, "vae"))
             vitp = vit_mod.siglip_to_generic(load_safetensors_dir(os.path.join(redux_dir, "image_encoder")), vitcfg)
             rp = load_safetensors_dir(os.path.join(redux_dir, "image_embedder"))
-        tr = FluxTransformerHIP(cfg, tp, dev)
+        tr = FluxTransformerHIP(cfg, tp, dev, linear_precision=linear_precision)
         vae = vae_mod.FluxVaeHIP(vcfg, vp, dev)
         del tp, vp
         self.cfg, self.vit_cfg = cfg, vitcfg

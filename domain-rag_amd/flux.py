@@ -33,6 +33,18 @@ _SEPARATE_QPREP = os.environ.get("DRAG_QPREP_SEPARATE", "") not in ("", "0")    
 # one round + 4.5 rounds of small tiles (1132 / 800-1000).  So the choice follows the library's own cost model per launch shape
 # (ops.gemm_cost: fused when it is >= 10 % cheaper); DRAG_QKV_MLP_FUSED=1 / =0 force it on / off.
 _FUSED_QKV_MLP = {"": None, "0": False}.get(os.environ.get("DRAG_QKV_MLP_FUSED", ""), True)
+# the precision of the blocks' Linears: "bf16" (default) or "mxfp8" (opt-in: OCP MXFP8 operands on the block-scaled matrix instruction,
+# ops.quantize_mxfp8 + ops.gemm_mxfp8); $DRAG_LINEAR_PRECISION sets the process default, read once
+LINEAR_PRECISIONS = ("bf16", "mxfp8")
+_LINEAR_PRECISION = os.environ.get("DRAG_LINEAR_PRECISION", "") or "bf16"
+if _LINEAR_PRECISION not in LINEAR_PRECISIONS:
+    raise ValueError(f"DRAG_LINEAR_PRECISION must be one of {LINEAR_PRECISIONS}, not {_LINEAR_PRECISION!r}")
+# Linear shapes (N, K) that stay on bf16 INSIDE "mxfp8" mode: those whose MX route, the quantise pass of the activations included, was
+# not faster than drag_gemm_bf16 in the interleaved same-process A/B of scripts/bench_gemm_mxfp8.py at the headline's 42 696 rows
+# (profiles/mxfp8_gemm_ab.log).  A shape that was not measured moves.  With the 128x128 MX kernel (800-890 TFLOP/s against 1348-1434 of
+# the bf16 GEMM) every headline shape measured (MX + quantise) / bf16 between 1.62 and 1.84, so all six stay; the single blocks' 21 504-row
+# weight runs as its 9216- and 12 288-row ranges on the MX route, both listed.
+_MX_STAYS_BF16: frozenset = frozenset({(9216, 3072), (3072, 3072), (12288, 3072), (3072, 12288), (21504, 3072), (3072, 15360)})
 
 
 def rope_tables(ids: torch.Tensor, axes_dims=(16, 56, 56), theta: float = 10000.0):
@@ -55,7 +67,9 @@ def latent_image_ids(h: int, w: int) -> torch.Tensor:
 
 
 class FluxTransformerHIP:
-    def __init__(self, cfg: FluxConfig, params: dict, device="cuda"):
+    def __init__(self, cfg: FluxConfig, params: dict, device="cuda", linear_precision: str | None = None):
+        """``linear_precision``: "bf16" | "mxfp8" (None: $DRAG_LINEAR_PRECISION, else "bf16") — also a settable attribute; the bf16
+        weights are kept in either mode, so one process can A/B"""
         if cfg.attention_head_dim != 128:
             raise ValueError("the HIP attention kernel is specialised for head_dim 128 (all FLUX.1 models)")
         self.cfg = cfg
@@ -127,6 +141,64 @@ class FluxTransformerHIP:
                 wo=g(p + "proj_out.weight"), bo=g(p + "proj_out.bias")))
         self._ws_key = None
         self._rope_key = None
+        self._mx_ready = False
+        self.linear_precision = linear_precision or _LINEAR_PRECISION
+
+    # ------------------------------------------------------------------ MXFP8 mode
+    # What moves (blocks only): both streams' to_q|k|v, the attention out-projections, ff up (+GELU) and ff down, the single blocks'
+    # q|k|v + proj_mlp and proj_out.  Embedders, the stacked modulation GEMV, the final proj_out and everything outside the DiT stay bf16.
+    _MX_DOUBLE = ("wqkv", "cwqkv", "wo", "cwo", "w1", "cw1", "w2", "cw2")
+    _MX_SINGLE = ("wqkvm", "wo")
+
+    @property
+    def linear_precision(self) -> str:
+        return self._linear_precision
+
+    @linear_precision.setter
+    def linear_precision(self, value: str) -> None:
+        if value not in LINEAR_PRECISIONS:
+            raise ValueError(f"linear_precision must be one of {LINEAR_PRECISIONS}, not {value!r}")
+        if value == "mxfp8" and not self._mx_ready:
+            # the weights' MX copies, by the kernel that quantises the activations (rows are quantised one by one: stacking changes nothing)
+            # (a weight none of whose launch shapes moves gets no copy)
+            D, F = self.cfg.dim, self.cfg.mlp_ratio * self.cfg.dim
+            self._linear_precision = value
+            for blocks, keys in ((self.double, self._MX_DOUBLE), (self.single, self._MX_SINGLE)):
+                for blk in blocks:
+                    for k in keys:
+                        N, K = blk[k].shape
+                        if self._mx_moves(N, K) if k != "wqkvm" else (self._mx_moves(3 * D, D) or self._mx_moves(F, D)):
+                            blk[k + "@mx"] = ops.quantize_mxfp8(blk[k])
+            self._mx_ready = True
+        self._linear_precision = value
+
+    def _mx_moves(self, N: int, K: int) -> bool:
+        return self._linear_precision == "mxfp8" and (N, K) not in _MX_STAYS_BF16 and K % 128 == 0 and N % 8 == 0
+
+    @staticmethod
+    def _mx_quant(ws, a, M, K, lda, rows_per_batch=0, batch_stride=0, row0=0):
+        """quantise one Linear input (rows addressed as ``ops.gemm``'s ``a``) into the workspace's scratch, from dense row ``row0`` on"""
+        out = (ws["mxq"][row0 * K:], ws["mxs"][row0 * (K // 32):])
+        return ops.quantize_mxfp8(a, M=M, K=K, lda=lda, rows_per_batch=rows_per_batch, batch_stride=batch_stride, out=out)
+
+    def _mx_gemm(self, ws, d, wmx, row0=0, qa=None):
+        """one Linear given as ``ops.gemm`` keywords (``a``, ``out`` included) on the MX route: quantise its input unless ``qa`` has it"""
+        M, K = d["M"], wmx[0].shape[1]
+        if qa is None:
+            qa = self._mx_quant(ws, d["a"], M, K, d.get("lda", K), d.get("a_rows_per_batch", 0), d.get("a_batch_stride", 0), row0)
+        ops.gemm_mxfp8(qa[0], qa[1], wmx[0], wmx[1], d["out"], bias=d.get("bias"), act=d.get("act", ops.ACT_NONE), act_n0=d.get("act_n0", 0),
+                       gate=d.get("gate"), resid=d.get("resid"), M=M, c_rows_per_batch=d.get("c_rows_per_batch", 0),
+                       c_batch_stride=d.get("c_batch_stride", 0), ldc=d["ldc"], ldg=d.get("ldg", 0))
+
+    def _pair(self, ws, blk, key1, d1, key2, d2):
+        """a double block's image / text Linear pair: ``ops.gemm_pair`` in bf16, two quantise + GEMM launches each on the MX route (there
+        is no MX pair form); the text rows' scratch follows the image rows'"""
+        if not self._mx_moves(*blk[key1].shape):
+            d1 = dict(d1, w=blk[key1]); d2 = dict(d2, w=blk[key2])
+            ops.gemm_pair(d1, d2)
+            return
+        self._mx_gemm(ws, d1, blk[key1 + "@mx"])
+        self._mx_gemm(ws, d2, blk[key2 + "@mx"], row0=d1["M"])
 
     # ------------------------------------------------------------------ workspaces
     def _workspace(self, B, St, Si):
@@ -202,6 +274,10 @@ class FluxTransformerHIP:
         S = St + Si
         ws = self._workspace(B, St, Si)
         x, nrm, qkv, vt, attn, catb, mod = ws["x"], ws["nrm"], ws["qkv"], ws["vt"], ws["attn"], ws["cat"], ws["mod"]
+        if "mxq" not in ws and any(self._mx_moves(n, k) for n, k in ((3 * D, D), (D, D), (F, D), (D, F), (D, D + F))):
+            # the widest Linear input (the single blocks' [attn | mlp], D + F columns) as e4m3 bytes + its e8m0 scales
+            ws["mxq"] = torch.empty(B * S * (D + F), dtype=torch.uint8, device=self.device)
+            ws["mxs"] = torch.empty(B * S * (D + F) // 32, dtype=torch.uint8, device=self.device)
         cos, sin = self._rope(txt_ids, img_ids)
         hidden = hidden.contiguous(); enc = enc.contiguous(); pooled = pooled.contiguous()
         Mi, Mt, M = B * Si, B * St, B * S
@@ -242,10 +318,10 @@ class FluxTransformerHIP:
             ops.layernorm(x, nrm_txt, Mt, D, scale=modv[cmo + D:], shift=modv[cmo:], ldx=D, rows_per_batch=St,
                           x_batch_stride=S * D, ld_mod=LM)
             # the image-stream and text-stream Linears of a pair share N and K: one launch when they are small alone (ops.gemm_pair)
-            ops.gemm_pair(dict(a=nrm_img, w=blk["wqkv"], out=qkv_img, bias=blk["bqkv"], M=Mi, lda=D, c_rows_per_batch=Si,
-                               c_batch_stride=S * 3 * D, ldc=3 * D),
-                          dict(a=nrm_txt, w=blk["cwqkv"], out=qkv, bias=blk["cbqkv"], M=Mt, lda=D, c_rows_per_batch=St,
-                               c_batch_stride=S * 3 * D, ldc=3 * D))
+            self._pair(ws, blk, "wqkv", dict(a=nrm_img, out=qkv_img, bias=blk["bqkv"], M=Mi, lda=D, c_rows_per_batch=Si,
+                                             c_batch_stride=S * 3 * D, ldc=3 * D),
+                       "cwqkv", dict(a=nrm_txt, out=qkv, bias=blk["cbqkv"], M=Mt, lda=D, c_rows_per_batch=St,
+                                     c_batch_stride=S * 3 * D, ldc=3 * D))
             if _SEPARATE_QPREP:     # A/B switch: the round-1 route (q prepared by the pass, plain attention)
                 ops.qk_norm_rope_vt(qkv, vt, blk["cnq"], blk["cnk"], blk["nq"], blk["nk"], cos, sin, B, S, H, 3 * D, St)
                 ops.attention(qkv, qkv.view(-1)[D:], vt, attn, B, S, H, 3 * D, S * 3 * D, D, S * D, scale)
@@ -254,32 +330,43 @@ class FluxTransformerHIP:
                 ops.k_norm_rope_vt(qkv, vt, blk["cnk"], blk["nk"], cos, sin, B, S, H, 3 * D, St)
                 ops.attention_qprep(qkv, qkv.view(-1)[D:], vt, attn, B, S, H, 3 * D, S * 3 * D, D, S * D, scale,
                                     blk["cnq"], blk["nq"], cos, sin, St)
-            ops.gemm_pair(dict(a=attn_img, w=blk["wo"], out=x_img, bias=blk["bo"], M=Mi, a_rows_per_batch=Si, a_batch_stride=S * D,
-                               lda=D, c_rows_per_batch=Si, c_batch_stride=S * D, ldc=D, gate=modv[mo + 2 * D:], resid=x_img, ldg=LM),
-                          dict(a=attn, w=blk["cwo"], out=x, bias=blk["cbo"], M=Mt, a_rows_per_batch=St, a_batch_stride=S * D,
-                               lda=D, c_rows_per_batch=St, c_batch_stride=S * D, ldc=D, gate=modv[cmo + 2 * D:], resid=x, ldg=LM))
+            self._pair(ws, blk, "wo", dict(a=attn_img, out=x_img, bias=blk["bo"], M=Mi, a_rows_per_batch=Si, a_batch_stride=S * D,
+                                           lda=D, c_rows_per_batch=Si, c_batch_stride=S * D, ldc=D, gate=modv[mo + 2 * D:], resid=x_img, ldg=LM),
+                       "cwo", dict(a=attn, out=x, bias=blk["cbo"], M=Mt, a_rows_per_batch=St, a_batch_stride=S * D,
+                                   lda=D, c_rows_per_batch=St, c_batch_stride=S * D, ldc=D, gate=modv[cmo + 2 * D:], resid=x, ldg=LM))
             # MLPs (the two streams are independent: both LayerNorms, both up-projections, both down-projections)
             ops.layernorm(x_img, nrm_img, Mi, D, scale=modv[mo + 4 * D:], shift=modv[mo + 3 * D:], ldx=D,
                           rows_per_batch=Si, x_batch_stride=S * D, ld_mod=LM)
             ops.layernorm(x, nrm_txt, Mt, D, scale=modv[cmo + 4 * D:], shift=modv[cmo + 3 * D:], ldx=D,
                           rows_per_batch=St, x_batch_stride=S * D, ld_mod=LM)
-            ops.gemm_pair(dict(a=nrm_img, w=blk["w1"], out=hid, bias=blk["b1"], act=ops.ACT_GELU_TANH, M=Mi, lda=D, ldc=F),
-                          dict(a=nrm_txt, w=blk["cw1"], out=hid_txt, bias=blk["cb1"], act=ops.ACT_GELU_TANH, M=Mt, lda=D, ldc=F))
-            ops.gemm_pair(dict(a=hid, w=blk["w2"], out=x_img, bias=blk["b2"], M=Mi, lda=F, c_rows_per_batch=Si,
-                               c_batch_stride=S * D, ldc=D, gate=modv[mo + 5 * D:], resid=x_img, ldg=LM),
-                          dict(a=hid_txt, w=blk["cw2"], out=x, bias=blk["cb2"], M=Mt, lda=F, c_rows_per_batch=St,
-                               c_batch_stride=S * D, ldc=D, gate=modv[cmo + 5 * D:], resid=x, ldg=LM))
+            self._pair(ws, blk, "w1", dict(a=nrm_img, out=hid, bias=blk["b1"], act=ops.ACT_GELU_TANH, M=Mi, lda=D, ldc=F),
+                       "cw1", dict(a=nrm_txt, out=hid_txt, bias=blk["cb1"], act=ops.ACT_GELU_TANH, M=Mt, lda=D, ldc=F))
+            self._pair(ws, blk, "w2", dict(a=hid, out=x_img, bias=blk["b2"], M=Mi, lda=F, c_rows_per_batch=Si,
+                                           c_batch_stride=S * D, ldc=D, gate=modv[mo + 5 * D:], resid=x_img, ldg=LM),
+                       "cw2", dict(a=hid_txt, out=x, bias=blk["cb2"], M=Mt, lda=F, c_rows_per_batch=St,
+                                   c_batch_stride=S * D, ldc=D, gate=modv[cmo + 5 * D:], resid=x, ldg=LM))
             if taps is not None:
                 taps[f"double.{i}"] = x.clone()
 
         cat_mlp = catb.view(-1)[D:]
         fused_qkv_mlp = (3 * D) % 256 == 0 and (_FUSED_QKV_MLP if _FUSED_QKV_MLP is not None else
                                                 ops.gemm_cost(M, 3 * D + F, D) * 10 <= (ops.gemm_cost(M, 3 * D, D) + ops.gemm_cost(M, F, D)) * 9)
+        mx_qkv, mx_mlp, mx_out = self._mx_moves(3 * D, D), self._mx_moves(F, D), self._mx_moves(D, D + F)
         for i, blk in enumerate(self.single):
             mo = self.mod_off[("s", i)]      # shift, scale, gate
             ops.layernorm(x, nrm, M, D, scale=modv[mo + D:], shift=modv[mo:], ldx=D, ld_mod=LM, rows_per_batch=S,
                           x_batch_stride=S * D)
-            if fused_qkv_mlp:
+            if mx_qkv or mx_mlp:
+                # one quantisation of the modulated LayerNorm output serves q|k|v and proj_mlp: two launches over the stacked weight's row
+                # ranges (a range whose shape stays on bf16 takes the bf16 GEMM)
+                qa = self._mx_quant(ws, nrm, M, D, D)
+                wq, wsc = blk["wqkvm@mx"]
+                for moves, lo, hi, dst, ldd, act_ in ((mx_qkv, 0, 3 * D, qkv, 3 * D, ops.ACT_NONE), (mx_mlp, 3 * D, 3 * D + F, cat_mlp, D + F, ops.ACT_GELU_TANH)):
+                    if moves:
+                        ops.gemm_mxfp8(qa[0], qa[1], wq[lo:hi], wsc[lo:hi], dst, bias=blk["bqkvm"][lo:hi], act=act_, M=M, ldc=ldd)
+                    else:
+                        ops.gemm(nrm, blk["wqkvm"][lo:hi], out=dst, bias=blk["bqkvm"][lo:hi], act=act_, M=M, lda=D, ldc=ldd)
+            elif fused_qkv_mlp:
                 ops.gemm(nrm, blk["wqkvm"], out=qkv, bias=blk["bqkvm"], act=ops.ACT_GELU_TANH, act_n0=3 * D, M=M, lda=D, ldc=3 * D,
                          out2=cat_mlp, ldc2=D + F, n_split=3 * D)
             else:       # (test-sized widths whose q|k|v block does not end on a tile boundary)
@@ -292,8 +379,12 @@ class FluxTransformerHIP:
                 ops.k_norm_rope_vt(qkv, vt, blk["nk"], blk["nk"], cos, sin, B, S, H, 3 * D, 0)
                 ops.attention_qprep(qkv, qkv.view(-1)[D:], vt, catb, B, S, H, 3 * D, S * 3 * D, D + F, S * (D + F), scale,
                                     blk["nq"], blk["nq"], cos, sin, 0)
-            ops.gemm(catb, blk["wo"], out=x, bias=blk["bo"], M=M, lda=D + F, c_rows_per_batch=S, c_batch_stride=S * D,
-                     ldc=D, gate=modv[mo + 2 * D:], resid=x, ldg=LM)
+            proj = dict(a=catb, out=x, bias=blk["bo"], M=M, lda=D + F, c_rows_per_batch=S, c_batch_stride=S * D,
+                        ldc=D, gate=modv[mo + 2 * D:], resid=x, ldg=LM)
+            if mx_out:
+                self._mx_gemm(ws, proj, blk["wo@mx"])
+            else:
+                ops.gemm(proj.pop("a"), blk["wo"], **proj)
             if taps is not None:
                 taps[f"single.{i}"] = x.clone()
 
@@ -315,12 +406,13 @@ class FluxTransformerHIP:
         A captured graph bakes in the addresses of everything the forward touched, so a cache entry OWNS its workspace,
         RoPE tables and time buffers (they must not be freed or reused while the graph lives), is keyed on the input
         addresses, the shapes AND the RoPE table identity (the same token count can be a different h x w), and the
-        cache is a small LRU (image sizes vary from sample to sample in stage 3)."""
+        cache is a small LRU (image sizes vary from sample to sample in stage 3).  The Linear precision is part of the key: the two modes
+        are different launch sequences."""
         t = torch.as_tensor(timestep, dtype=torch.float32).cpu().reshape(-1)
         g = None if guidance is None else torch.as_tensor(guidance, dtype=torch.float32).cpu().reshape(-1)
         rope_key = self._ids_key(txt_ids, img_ids)
         key = (hidden.data_ptr(), enc.data_ptr(), pooled.data_ptr(), tuple(hidden.shape), tuple(enc.shape), tuple(pooled.shape),
-               guidance is None, rope_key)
+               guidance is None, rope_key, self._linear_precision)
         cache = self.__dict__.setdefault("_graphs", {})
         ent = cache.pop(key, None)
         if ent is None:

@@ -13,7 +13,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import GemmArgs, check
+from ._lib import GemmArgs, GemmMxArgs, check
 
 ACT_NONE, ACT_GELU_TANH, ACT_SILU, ACT_QUICK_GELU, ACT_GELU_ERF = 0, 1, 2, 3, 4
 
@@ -44,6 +44,8 @@ class GemmRecorder:
         the library's own tile policy); ``conv`` = ("pair", M1, M2) for a merged pair launch"""
         if conv == "f32":
             return "conv2d_f32_kernel"
+        if conv == "mx":                                     # drag_gemm_mxfp8: one kernel so far
+            return "gemm_mxfp8_simple"
         M, N, K = shape
         if isinstance(conv, tuple) and conv[0] == "splitk":  # drag_gemm_bf16 as stacked K slices + the reduce pass (one recorded interval)
             return "gemm_bf16_w4p + splitk_reduce_kernel"
@@ -346,6 +348,89 @@ def gemm_pair(first: dict, second: dict):
             sl = lib.drag_gemm_bf16_splitk_slices(ctypes.byref(args_i)) if _recorder is not None else 0
             _recorded(lambda: check(lib.drag_gemm_bf16(ctypes.byref(args_i), _stream()), "drag_gemm_bf16"), s_i, ("splitk", sl) if sl else False)
     return o1, o2
+
+
+def quantize_mxfp8(x: torch.Tensor, *, M: int | None = None, K: int | None = None, lda: int | None = None, rows_per_batch: int = 0,
+                   batch_stride: int = 0, out=None):
+    """bf16 rows -> OCP MXFP8 ``(q, s)`` (``drag_quantize_mxfp8``): ``q`` uint8 [M, K] e4m3fn bytes, ``s`` uint8 [M, K / 32] e8m0 bytes,
+    both dense.  ``x`` may be a view into a larger buffer: pass the logical row count ``M``, the width ``K`` and the batched-row
+    addressing (``lda``, ``rows_per_batch``, ``batch_stride``) as for ``gemm``'s ``a``; by default ``x`` is a dense [M, K] matrix.
+    ``out`` = (q, s) buffers to write into (at least M * K and M * K / 32 bytes).  The rule: :mod:`.mx`."""
+    _need(x, torch.bfloat16, "quantize_mxfp8.x")
+    if K is None:
+        K = x.shape[-1]
+    if M is None:
+        if x.dim() != 2 or x.stride(-1) != 1 or x.shape[1] != K:
+            raise ValueError("quantize_mxfp8.x: without M, a 2-D [M, K] matrix with unit inner stride is expected (pass M and the row map for a view)")
+        M = x.shape[0]
+        if lda is None:
+            lda = x.stride(0)
+    if lda is None:
+        lda = K
+    if K % 128:
+        raise ValueError(f"quantize_mxfp8: K = {K} must be a multiple of 128")
+    # the last element read must lie inside x's storage: a wrong row map is an error here, not a memory fault there
+    rpb = rows_per_batch if 0 < rows_per_batch < M else M
+    last = ((M - 1) // rpb) * batch_stride + ((M - 1) % rpb) * lda + K
+    if last > _room(x):
+        raise ValueError(f"quantize_mxfp8.x: {M} rows of this row map end at element {last}, past the source ({_room(x)} elements from its start)")
+    if out is None:
+        q = torch.empty((M, K), dtype=torch.uint8, device=x.device)
+        s = torch.empty((M, K // 32), dtype=torch.uint8, device=x.device)
+    else:
+        q, s = out
+        _need(q, torch.uint8, "quantize_mxfp8.out[0]")
+        _need(s, torch.uint8, "quantize_mxfp8.out[1]")
+        if not (q.is_contiguous() and s.is_contiguous()) or q.numel() < M * K or s.numel() < M * (K // 32):
+            raise ValueError("quantize_mxfp8.out: contiguous buffers of at least M * K and M * K / 32 bytes")
+    check(_lib.load().drag_quantize_mxfp8(_p(x), M, K, lda, rows_per_batch, batch_stride, _p(q), _p(s), _stream()), "drag_quantize_mxfp8")
+    return q, s
+
+
+def gemm_mxfp8(aq: torch.Tensor, ascale: torch.Tensor, wq: torch.Tensor, wscale: torch.Tensor, out: torch.Tensor | None = None, *,
+               bias=None, act: int = ACT_NONE, act_n0: int = 0, gate=None, resid=None, M: int | None = None,
+               c_rows_per_batch: int = 0, c_batch_stride: int = 0, ldc: int | None = None, ldg: int = 0) -> torch.Tensor:
+    """out = epi(dequant(aq, ascale) @ dequant(wq, wscale).T), bf16 (``drag_gemm_mxfp8``): operands as ``quantize_mxfp8`` writes them
+    (``wq`` [N, K], ``wscale`` [N, K / 32]; ``aq`` / ``ascale`` may be larger scratch buffers holding ``M`` dense rows), the epilogue
+    arguments as ``gemm``'s."""
+    for t, name in ((aq, "aq"), (ascale, "ascale"), (wq, "wq"), (wscale, "wscale")):
+        _need(t, torch.uint8, "gemm_mxfp8." + name)
+        if not t.is_contiguous():
+            raise ValueError(f"gemm_mxfp8.{name} must be contiguous")
+    if wq.dim() != 2 or wscale.dim() != 2:
+        raise ValueError("gemm_mxfp8: wq [N, K] and wscale [N, K / 32] expected")
+    N, K = wq.shape
+    if K % 128 or tuple(wscale.shape) != (N, K // 32):
+        raise ValueError(f"gemm_mxfp8: K = {K} must be a multiple of 128 and wscale [N, K / 32] (got {tuple(wscale.shape)})")
+    if M is None:
+        M = aq.numel() // K
+    if aq.numel() < M * K or ascale.numel() < M * (K // 32):
+        raise ValueError(f"gemm_mxfp8: aq / ascale hold fewer than M = {M} rows of K = {K}")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=aq.device)
+    _need(out, torch.bfloat16, "gemm_mxfp8.out")
+    if ldc is None:
+        ldc = out.stride(-2) if out.dim() >= 2 and out.stride(-1) == 1 else N
+    # the last element addressed must lie inside each tensor's storage: a wrong row map is an error here, not a memory fault there
+    rpb = c_rows_per_batch if 0 < c_rows_per_batch < M else M
+    last = ((M - 1) // rpb) * c_batch_stride + ((M - 1) % rpb) * ldc + N
+    nb = (M - 1) // rpb + 1
+    for t, name, need in ((out, "out", last), (resid, "resid", last), (bias, "bias", N), (gate, "gate", (nb - 1) * ldg + N)):
+        if t is None:
+            continue
+        _need(t, torch.bfloat16, "gemm_mxfp8." + name)
+        if need > _room(t):
+            raise ValueError(f"gemm_mxfp8.{name}: the launch addresses {need} elements from its start, the tensor holds {_room(t)}")
+    args = GemmMxArgs()
+    args.Aq, args.Ascale, args.Wq, args.Wscale, args.C = aq.data_ptr(), ascale.data_ptr(), wq.data_ptr(), wscale.data_ptr(), out.data_ptr()
+    args.bias = bias.data_ptr() if bias is not None else None
+    args.gate = gate.data_ptr() if gate is not None else None
+    args.resid = resid.data_ptr() if resid is not None else None
+    args.M, args.N, args.K = M, N, K
+    args.ldc, args.c_rows_per_batch, args.c_batch_stride = ldc, c_rows_per_batch, c_batch_stride
+    args.ldg, args.act, args.act_n0 = ldg, act, act_n0
+    _recorded(lambda: check(_lib.load().drag_gemm_mxfp8(ctypes.byref(args), _stream()), "drag_gemm_mxfp8"), (M, N, K), "mx")
+    return out
 
 
 def qk_norm_rope_vt(qkv: torch.Tensor, vt: torch.Tensor, wq_txt, wk_txt, wq_img, wk_img, rope_cos, rope_sin,

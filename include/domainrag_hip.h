@@ -52,6 +52,9 @@ const char* drag_last_error(void);
  *   "gemm_w4"             0 | 1 | 2 | 3   gemm_bf16_w4p by policy | never | wherever it can run | launches of >= 256 tiles
  *   "gemm_splitk"         0 | 1 | n       split-K by policy | never | n slices wherever valid (see drag_gemm_set_workspace); a split launch sums
  *                                         its slices' f32 chains: the last bit may differ
+ *   "gemm_mx_kernel"      0 | 1 | 2       drag_gemm_mxfp8: by policy | the 128x128 kernel | the wide (256x256, persistent) kernel; the wide
+ *                                         kernel is not built yet: the policy gives every launch to the 128x128 kernel and 2 is refused
+ *                                         at the launch
  *   "ln_generic"          0 | 1           the any-width LayerNorm kernel where the fixed-width (3072) one would apply
  *   "conv_no_small_cout"  0 | 1           drag_conv2d_f32 without its kernel for <= 4 output channels
  *   "conv_no_lin"         0 | 1           drag_conv2d_f32: the general form (per-load predicates) for 1x1 convolutions too
@@ -149,6 +152,38 @@ int drag_gemm_bf16_splitk_slices(const drag_gemm_args* args);
 /* the same for drag_gemm_bf16_pair(a, b): a pair that splits runs ONE partial launch over both problems' rows (same row stride of A required)
  * and one reduce pass per problem */
 int drag_gemm_bf16_pair_splitk_slices(const drag_gemm_args* a, const drag_gemm_args* b);
+
+/* ---------------------------------------------------------------------------------------
+ * OCP MXFP8 (opt-in low-precision Linears of the Flux DiT; the default path is bf16 and calls neither of these).
+ * Storage: elements are e4m3fn bytes, dense [rows, K], K % 128 == 0; scales are e8m0 bytes, dense [rows, K / 32], one per block of 32
+ * consecutive K elements, byte b = 2^(b - 127).
+ *
+ * drag_quantize_mxfp8 — bf16 rows -> (q, scales), one pass.  Logical row r of x lives at
+ *   x + (r / rows_per_batch) * batch_stride + (r % rows_per_batch) * ldx   (elements; rows_per_batch <= 0: one batch), as A of drag_gemm_bf16;
+ * the outputs are dense.  Per block: amax = max |x|; e = the smallest integer with amax * 2^-e <= 448 (with amax = m 2^E, 1 <= m < 2:
+ * E - 8 for m <= 1.75, else E - 7; taken from the bits), clamped to [-127, 127]; scale byte = e + 127 (an all-zero block: 127, zero
+ * elements); elements = x * 2^-e rounded to nearest-even to e4m3fn, saturated at +-448 (reachable only when e was clamped).  Bit-exact
+ * against domain-rag_amd/mx.py quantize_ref.  Non-finite inputs are outside the contract (their bytes are unspecified).
+ * Requires K % 128 == 0, ldx >= K, ldx % 8 == 0, batch_stride % 8 == 0, x 16-byte, q 8-byte and scales 4-byte aligned.
+ * Weights are quantised with this same kernel when a model is built. */
+int drag_quantize_mxfp8(const void* x, int64_t rows, int32_t K, int32_t ldx, int32_t rows_per_batch, int64_t batch_stride,
+                        void* q, void* scales, void* stream);
+/* drag_gemm_mxfp8 — C = epi(dequant(Aq, Ascale)[M,K] . dequant(Wq, Wscale)[N,K]^T), bf16 output, fp32 accumulation on the block-scaled
+ * matrix instruction (v_mfma_scale_f32_16x16x128_f8f6f4, e4m3 operands): one MFMA per 128-K step of a 16x16 output block, K-steps in
+ * ascending order, so every output element has one accumulation chain whichever kernel computes it.  Operands dense as described above.
+ * The epilogue is drag_gemm_bf16's (same code): v = acc + bias[n]; v = act(v) for n >= act_n0; gate != NULL: C = resid + gate[r /
+ * c_rows_per_batch, n] * v with torch's bf16 roundings; else resid != NULL: C = resid + v; C / resid rows addressed by (ldc,
+ * c_rows_per_batch, c_batch_stride) as there.  Requires K % 128 == 0, N % 8 == 0, ldc % 4 == 0, c_batch_stride % 4 == 0, Aq / Wq 16-byte
+ * aligned, scale rows 4-byte aligned (they are: K / 32 is a multiple of 4), C / bias / gate / resid 8-byte aligned. */
+typedef struct drag_gemm_mx_args {
+  const void *Aq, *Ascale, *Wq, *Wscale;   /* [M,K] / [M,K/32] / [N,K] / [N,K/32] */
+  void* C;
+  const void *bias, *gate, *resid;
+  int32_t M, N, K, ldc, c_rows_per_batch;
+  int64_t c_batch_stride;
+  int32_t ldg, act, act_n0;
+} drag_gemm_mx_args;
+int drag_gemm_mxfp8(const drag_gemm_mx_args* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * drag_conv3x3_bf16 — 3x3 convolution as an implicit GEMM on the same MFMA main loop.
