@@ -22,7 +22,7 @@ import os, re, subprocess, sys, tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 # source -> substrings of the kernel names build.py checks in the object it ships
-CHECKED = {"attention.hip": ["attention_q64"], "gemm_bf16_w4p.hip": ["gemm_bf16_w4"],
+CHECKED = {"attention_q64.hip": ["attention_q64"], "attention_q64g.hip": ["attention_q64"], "gemm_bf16_w4p.hip": ["gemm_bf16_w4"],
            "gemm_bf16_deep_n128.hip": ["gemm_bf16_deep"], "gemm_bf16_deep_n192a.hip": ["gemm_bf16_deep"], "gemm_bf16_deep_n192b.hip": ["gemm_bf16_deep"]}
 REG = re.compile(r"\b([va])(?:(\d+)|\[(\d+):(\d+)\])")
 

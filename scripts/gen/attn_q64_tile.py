@@ -1,4 +1,4 @@
-"""Generator (+ CPU emulator and hazard checker) of attention_q64g_kernel's KV loop (csrc/attention.hip): ONE asm statement per item
+"""Generator (+ CPU emulator and hazard checker) of attention_q64g_kernel's KV loop (csrc/attention_q64g.hip): ONE asm statement per item
 (256 queries of one (batch, head); this wave's 64 of them against every KV tile) — prologue scores, every tile, the final P V.
 
     python scripts/gen/attn_q64_tile.py > domain-rag_amd/csrc/attn_q64_tile.h

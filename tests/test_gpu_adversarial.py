@@ -543,7 +543,7 @@ def test_qk_norm_rope_vt_row_norms_from_1e_minus_20_to_1e18(gpu):
                                "rows (10^exponent of their scale):", sorted({(int(i[2]), exps[int(i[2]) // 4]) for i in bad.nonzero()})[:12])
     assert torch.equal(got[..., 2 * D:], qkv[..., 2 * D:])
     v = qkv[..., 2 * D:].view(B, S, H, 128)
-    # V^T image: keys permuted inside 16-groups (csrc/attention.hip); compare as sets per (head, d, 16-key group)
+    # V^T image: keys permuted inside 16-groups (csrc/attention_prep.hip); compare as sets per (head, d, 16-key group)
     vtc = vt.cpu()[..., :S - S % 16].view(B, H, 128, -1, 16).float().sort(-1).values
     vr = v.permute(0, 2, 3, 1)[..., :S - S % 16].reshape(B, H, 128, -1, 16).float().sort(-1).values
     assert torch.equal(vtc, vr)
