@@ -1,6 +1,7 @@
 // attention.hip — the host side of the attention kernels: which kernel a call takes, the launches, the C ABI.  The kernels and what they share
 // are described in attention_kernels.h; each is compiled from its own source.
 #include "attention_kernels.h"
+#include "drag_launch.h"
 
 using namespace drag_attn;
 
@@ -116,57 +117,61 @@ extern "C" int drag_attention_v_bf16(const void* q, const void* k, const void* v
 static int persist_slots() {
   const int opt = drag_opt(DRAG_OPT_ATTN_PERSIST);
   if (opt >= 3) return opt;           // (1 = one per CU)
-  static int ncu8 = 0;
-  if (ncu8 == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    ncu8 = n / 8 > 0 ? n / 8 : 1;
-  }
-  return ncu8;
+  const int ncu8 = drag_cu_count() / 8;
+  return ncu8 > 0 ? ncu8 : 1;
 }
 #endif
 
 // ---- the launches: attention_launch picks one of these; every instantiation is named once, below ----
 using LaunchFn = int (*)(dim3 grid, int block, int lds, hipStream_t st, const AttnArgs& p);
 
-// more dynamic LDS than the default limit has to be allowed once per device and kernel (the attribute belongs to the device's copy of the kernel)
-template <auto Kernel>
-static int allow_dynamic_lds(int bytes) {
-  static unsigned long long ready = 0;       // one bit per device
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (!((ready >> (dev & 63)) & 1ull)) {
-    DRAG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess,
-               "drag_attention: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-    ready |= 1ull << (dev & 63);
-  }
-  return 0;
-}
-
-template <auto Kernel>
-static int launch(dim3 grid, int block, int lds, hipStream_t st, const AttnArgs& p) {
-  if (lds != 0 && allow_dynamic_lds<Kernel>(lds) != 0) return -1;
-  hipLaunchKernelGGL(Kernel, grid, dim3(block), lds, st, p);
-  return 0;
-}
-
 // attention_d128_kernel<NW, ..., QP, ...> by schedule: "attn_sched" 0 | 1 | 2 (and above) = schedule 1 + pipelined row maxima, the product's |
 // 3 in experiment builds = V^T fragments read a step ahead | row-major V (the product schedule only)
 enum { D128_S0, D128_S1, D128_S1_PMAX, D128_S3, D128_VROW, D128_FORMS };
 template <int NW, bool QP>
 constexpr LaunchFn d128_forms[D128_FORMS] = {
-    launch<attention_d128_kernel<NW, 0, QP, false>>, launch<attention_d128_kernel<NW, 1, QP, false>>, launch<attention_d128_kernel<NW, 1, QP, true>>,
-    launch<attention_d128_kernel<NW, DRAG_EXP ? 2 : 1, QP, true>>,      // (product builds: the D128_S1_PMAX entry again; never looked up there)
-    launch<attention_d128_kernel<NW, 1, QP, true, true>>};
+    drag_launch<attention_d128_kernel<NW, 0, QP, false>>, drag_launch<attention_d128_kernel<NW, 1, QP, false>>, drag_launch<attention_d128_kernel<NW, 1, QP, true>>,
+    drag_launch<attention_d128_kernel<NW, DRAG_EXP ? 2 : 1, QP, true>>,      // (product builds: the D128_S1_PMAX entry again; never looked up there)
+    drag_launch<attention_d128_kernel<NW, 1, QP, true, true>>};
 static const LaunchFn* d128_form(bool w8, bool qprep) {
   return w8 ? (qprep ? d128_forms<8, true> : d128_forms<8, false>) : (qprep ? d128_forms<4, true> : d128_forms<4, false>);
 }
+// (what bench.py's roofline prints for this family: block size and q preparation only)
+static const char* d128_name(bool w8, bool qprep) {
+  return w8 ? (qprep ? "attention_d128_kernel<8, ..., true, ...>" : "attention_d128_kernel<8, ..., false, ...>")
+            : (qprep ? "attention_d128_kernel<4, ..., true, ...>" : "attention_d128_kernel<4, ..., false, ...>");
+}
+
+// a 64-query kernel: its launch and its name, written once
+struct Q64Kernel { LaunchFn launch; const char* name; };
+#define DRAG_Q64(...) Q64Kernel{drag_launch<__VA_ARGS__>, #__VA_ARGS__}
 #if DRAG_EXP
 // "attn_gen" = 11 .. 29: schedule variants 1 .. 19 of the fold form
-#define DRAG_AQV_LAUNCH(V_) launch<attention_q64g_kernel<true, true, V_>>,
-constexpr LaunchFn q64g_variants[19] = {DRAG_ATTN_Q64G_VARIANTS(DRAG_AQV_LAUNCH)};
+#define DRAG_AQV_LAUNCH(V_) DRAG_Q64(attention_q64g_kernel<true, true, V_>),
+static const Q64Kernel q64g_variants[19] = {DRAG_ATTN_Q64G_VARIANTS(DRAG_AQV_LAUNCH)};
 #undef DRAG_AQV_LAUNCH
 #endif
+// the 64-query kernel a call over S keys takes.  "attn_gen": 0 = policy — the generated stream (attention_q64g_kernel) whenever the tiles
+// pair up, FOLD with the fused q preparation; 1 = never (attention_q64_kernel); 2 = the generated stream WITHOUT the fold (same bits as
+// attention_q64_kernel: tests, A/B)
+static Q64Kernel q64_kernel(int32_t S, bool qprep) {
+  const int gen = drag_opt(DRAG_OPT_ATTN_GEN);
+  if (!attention_generated(S)) return qprep ? DRAG_Q64(attention_q64_kernel<true>) : DRAG_Q64(attention_q64_kernel<false>);
+  if (!qprep) return DRAG_Q64(attention_q64g_kernel<false, false>);
+#if DRAG_EXP
+  if (gen >= 11 && gen <= 29) return q64g_variants[gen - 11];
+#endif
+  return gen != 2 ? DRAG_Q64(attention_q64g_kernel<true, true>) : DRAG_Q64(attention_q64g_kernel<true, false>);
+}
+#undef DRAG_Q64
+
+// the kernel the next launch of that shape takes under the current switches, as a profiler prints it — for callers that account launches
+// per kernel (asked BEFORE the launch: what the launch is about to read is what gets reported)
+extern "C" const char* drag_attention_bf16_kernel_name(int32_t S, int32_t v_row_major, int32_t q_prep) {
+  bool w8, q64;
+  attention_family(S, v_row_major != 0, w8, q64);
+  return q64 ? q64_kernel(S, q_prep != 0).name : d128_name(w8, q_prep != 0);
+}
 
 static int attention_launch(const void* q, const void* k, const void* vt, void* out, int32_t B, int32_t S, int32_t H,
                             int32_t ld_qk, int64_t qk_batch_stride, int32_t ld_o, int64_t o_batch_stride, float scale,
@@ -210,13 +215,7 @@ static int attention_launch(const void* q, const void* k, const void* vt, void* 
     // 64 KiB of tiles + 64 KiB for the q rows of the next item (LDS-DMA).  One workgroup per CU walks the items (persistent) when every
     // item exists (B * H a multiple of 8) and the tiles pair up (an even number, >= 4: the stream's last two tiles stage for the next item);
     // otherwise, and under "attn_walk" = 2, one item per workgroup
-    static int ncu64 = 0;
-    if (ncu64 == 0) {
-      int dev = 0, n = 0;
-      (void)hipGetDevice(&dev);
-      if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-      ncu64 = (n & ~7) ? (n & ~7) : 8;
-    }
+    const int ncu64 = (drag_cu_count() & ~7) ? (drag_cu_count() & ~7) : 8;
     p.items = (int)grid.x;
     const int nkv64 = p.s_pad / 64;
     const int popt = drag_opt(DRAG_OPT_ATTN_WALK);             // 0 policy | 2 one item per workgroup | n >= 8 (a multiple of 8): n workgroups (tests: many items each)
@@ -226,15 +225,7 @@ static int attention_launch(const void* q, const void* k, const void* vt, void* 
     lgrid = dim3(walk ? (unsigned)pgrid : grid.x);
     block = 256;
     lds = 2 * KT_BYTES + 2 * VT_BYTES + 4 * 16384;
-    // "attn_gen": 0 = policy — the generated stream (attention_q64g_kernel) whenever the tiles pair up, FOLD with the fused q preparation;
-    // 1 = never (attention_q64_kernel); 2 = the generated stream WITHOUT the fold (same bits as attention_q64_kernel: tests, A/B)
-    const int gen = drag_opt(DRAG_OPT_ATTN_GEN);
-    if (!attention_generated(S)) fn = qprep ? launch<attention_q64_kernel<true>> : launch<attention_q64_kernel<false>>;
-    else if (!qprep) fn = launch<attention_q64g_kernel<false, false>>;
-#if DRAG_EXP
-    else if (gen >= 11 && gen <= 29) fn = q64g_variants[gen - 11];
-#endif
-    else fn = gen != 2 ? launch<attention_q64g_kernel<true, true>> : launch<attention_q64g_kernel<true, false>>;
+    fn = q64_kernel(S, qprep).launch;
 #if DRAG_EXP
   } else if (w8 && sched == 2 && drag_opt(DRAG_OPT_ATTN_PERSIST) != 0 && fits32 && (B * H) % 8 == 0 && (p.s_pad / 64) % 2 == 0 &&
              nqb2 * groups > persist_slots()) {
@@ -247,12 +238,10 @@ static int attention_launch(const void* q, const void* k, const void* vt, void* 
     // dispatch; and the hardware already overlaps the seams of one-item workgroups (a CU holds two of them by LDS and registers, so
     // the next workgroup's waves start on SIMDs as the old one's retire), which a single persistent workgroup cannot do.
     lgrid = dim3(8 * persist_slots());
-    fn = qprep ? launch<attention_d128_kernel<8, 1, true, true, false, true>> : launch<attention_d128_kernel<8, 1, false, true, false, true>>;
+    fn = qprep ? drag_launch<attention_d128_kernel<8, 1, true, true, false, true>> : drag_launch<attention_d128_kernel<8, 1, false, true, false, true>>;
 #endif  // DRAG_EXP
   } else {
     fn = d128_form(w8, qprep)[DRAG_EXP && sched == 3 ? D128_S3 : sched >= 2 ? D128_S1_PMAX : sched == 1 ? D128_S1 : D128_S0];
   }
-  if (fn(lgrid, block, lds, st, p) != 0) return -1;
-  DRAG_LAUNCH_CHECK();
-  return 0;
+  return fn(lgrid, block, lds, st, p);
 }

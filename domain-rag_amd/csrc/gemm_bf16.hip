@@ -9,6 +9,8 @@
 // This file is the host side: tile policy, launch, split-K and the C ABI.  The kernels, their shared epilogue code and what each is for:
 // gemm_bf16_kernels.h and the gemm_bf16_*.hip sources it names.
 #include "gemm_bf16_kernels.h"
+#include "drag_launch.h"
+#include <stdio.h>
 #include <stdlib.h>
 
 using namespace drag_gemm;
@@ -106,16 +108,63 @@ static int deep_policy(long long M1, long long M2, int N, int K, long long* cost
 
 // persistent grid of the 256x256 kernel: one workgroup per CU (128 KiB of LDS each), fewer when there are fewer tiles
 static int t256_grid(int ntiles) {
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    ncu = n & ~7;                                  // multiple of the 8 XCDs, so a workgroup's tiles stay on its XCD's L2
-    if (ncu == 0) ncu = 8;
-  }
   if (drag_opt(DRAG_OPT_GEMM_NONPERSISTENT)) return ntiles;
+  int ncu = drag_cu_count() & ~7;                  // multiple of the 8 XCDs, so a workgroup's tiles stay on its XCD's L2
+  if (ncu == 0) ncu = 8;
   return ntiles < ncu ? ntiles : ncu;
+}
+
+// ---- THE table of the kernels behind drag_gemm_bf16 / drag_gemm_bf16_pair / drag_conv3x3_bf16: one row per code ("gemm_kernel",
+// drag_gemm_bf16_choice) with everything a launch needs.  gemm_launch, the "not built" refusal, drag_gemm_bf16_kernel_code and
+// drag_gemm_bf16_kernel_name read it; the ring rows come from the lists of gemm_bf16_kernels.h.
+namespace drag_gemm {
+using LaunchFn = int (*)(dim3 grid, int block, int lds, hipStream_t st, const GemmKArgs& p);
+// a code's kernel per form: batched rows | a merged pair, where that is a kernel of its own (else the rows kernel runs it) | conv3x3
+enum { FORM_ROWS, FORM_PAIR, FORM_CONV, FORMS };
+struct KernelForm { const char* name; LaunchFn launch; };      // the name as a profiler prints it; {null, null}: not built
+struct KernelRow {
+  int code, tm, tn, block, lds;      // tile rows x columns, threads per workgroup, dynamic LDS bytes
+  bool persistent;                   // one workgroup per CU walks the tiles (t256_grid), else one workgroup per tile
+  KernelForm form[FORMS];
+};
+#define DRAG_FORM(...) {#__VA_ARGS__, drag_launch<__VA_ARGS__>}
+#define DRAG_NI_NAME_4 ""
+#define DRAG_NI_NAME_6 ", 6"
+#define DRAG_DEEP_ROW(MI_, ST_, NI_)                                                                                       \
+  {(NI_ == 6 ? 100 : 0) + 10 * MI_ + ST_, 32 * MI_, 32 * NI_, 256, ST_ * (32 * MI_ + 32 * NI_) * 128, false,              \
+   {{"gemm_bf16_deep<" #MI_ ", " #ST_ DRAG_NI_NAME_##NI_ ">", drag_launch<gemm_bf16_deep<MI_, ST_, NI_>>}}},
+#define DRAG_W4_ROW(V_) {400 + V_, 256, 256, 256, 131072, false, {DRAG_FORM(gemm_bf16_w4<V_>)}},
+constexpr KernelRow kernel_table[] = {
+    {0, BM, BN, 256, 0, false, {DRAG_FORM(gemm_bf16_t128<0>), {}, DRAG_FORM(gemm_bf16_t128<1>)}},
+    {2, 256, 256, 512, 0, true, {DRAG_FORM(gemm_bf16_t256<0>), DRAG_FORM(gemm_bf16_t256_pair), DRAG_FORM(gemm_bf16_t256<1>)}},
+    {3, 256, 256, 256, 131072 + 4 * 4096, true, {DRAG_FORM(gemm_bf16_w4p)}},      // one segment, K % 128 == 0: gemm_choice
+    DRAG_GEMM_DEEP_N128(DRAG_DEEP_ROW) DRAG_GEMM_DEEP_N192A(DRAG_DEEP_ROW) DRAG_GEMM_DEEP_N192B(DRAG_DEEP_ROW)
+#if DRAG_EXP
+    DRAG_GEMM_W4_VARIANTS(DRAG_W4_ROW)      // round-5 experiment: gemm_bf16_w4<variant>
+#endif
+};
+#undef DRAG_FORM
+#undef DRAG_DEEP_ROW
+#undef DRAG_W4_ROW
+constexpr int kernel_rows = (int)(sizeof(kernel_table) / sizeof(kernel_table[0]));
+
+static const KernelRow* kernel_row(int code) {
+  for (const KernelRow& r : kernel_table)
+    if (r.code == code) return &r;
+  return nullptr;
+}
+}  // namespace drag_gemm
+
+// one form of a row over the k.tiles_m x k.tiles_n tiles of k
+static int launch_row(const KernelRow& row, int form, const GemmKArgs& k, void* stream) {
+  const int tiles = k.tiles_m * k.tiles_n;
+  return row.form[form].launch(dim3(row.persistent ? t256_grid(tiles) : tiles), row.block, row.lds, (hipStream_t)stream, k);
+}
+
+extern "C" int32_t drag_gemm_bf16_kernel_code(int32_t index) { return index >= 0 && index < kernel_rows ? kernel_table[index].code : -1; }
+extern "C" const char* drag_gemm_bf16_kernel_name(int32_t code, int32_t form) {
+  const KernelRow* row = kernel_row(code);
+  return row != nullptr && form >= 0 && form < FORMS ? row->form[form].name : nullptr;
 }
 
 static int fill_common(GemmKArgs& k, const void* A, const void* W, void* C, const void* bias, const void* gate,
@@ -226,85 +275,24 @@ static int gemm_launch(const drag_gemm_args* a, const drag_gemm_args* b, void* s
     k.M2 = k2.M; k.ldg2 = k2.ldg; k.wide2 = k2.wide; k.am2 = k2.am; k.cm2 = k2.cm;
   }
   const int choice = w_total_k > 0 ? 3 : gemm_choice(a->M, b ? b->M : 0, a->N, a->K);      // (the W offsets of the slices exist in gemm_bf16_w4p only)
-  const hipStream_t st_ = (hipStream_t)stream;
-  auto tiles_of = [&](int tm) {            // each segment starts on a tile boundary
-    k.tiles_m = (a->M + tm - 1) / tm;
-    if (b) { k.seg_tiles_m = k.tiles_m; k.tiles_m += (b->M + tm - 1) / tm; }
-  };
-  if (choice == 3) {            // the 4-wave persistent kernel (one segment, K % 128 == 0: gemm_choice)
-    k.tiles_m = (a->M + 255) / 256; k.tiles_n = (a->N + 255) / 256;
-    // its own tile walk (profiles/r05_gemm_w4p_group_m.log, interleaved, TFLOP/s at g = 2 | 4 | 8): (42 696, 21 504, 3072) 1468 | 1449 | 1419,
-    // (32 768, 9216, 3072) 1473 | 1497 | 1481, (32 768, 3072, 12 288) 1520 | 1528 | 1513, (32 768, 3072, 3072) 1456 | 1423 | 1451
-    if (drag_opt(DRAG_OPT_GEMM_GROUP_M) <= 0) k.group_m = a->N >= 16384 ? 2 : (a->N <= 3072 && a->K < 8192 ? 8 : 4);
-    constexpr int lds4 = 131072 + 4 * 4096;
-    static unsigned long long ready4 = 0;       // one bit per device: the attribute belongs to the device's copy of the kernel
-    int dev4 = 0;
-    (void)hipGetDevice(&dev4);
-    if (!((ready4 >> (dev4 & 63)) & 1ull)) {
-      DRAG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_w4p), hipFuncAttributeMaxDynamicSharedMemorySize, lds4) == hipSuccess,
-                 "drag_gemm_bf16: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-      ready4 |= 1ull << (dev4 & 63);
-    }
-    hipLaunchKernelGGL(gemm_bf16_w4p, dim3(t256_grid(k.tiles_m * k.tiles_n)), dim3(256), lds4, st_, k);
-  } else if (choice == 2) {
-    tiles_of(256); k.tiles_n = (a->N + 255) / 256;
-    const dim3 g(t256_grid(k.tiles_m * k.tiles_n));
-    if (b) hipLaunchKernelGGL(gemm_bf16_t256_pair, g, dim3(512), 0, st_, k);
-    else hipLaunchKernelGGL((gemm_bf16_t256<0>), g, dim3(512), 0, st_, k);
-  } else if (choice) {
-    const int deep = choice;
-    const int ni = deep >= 100 ? 6 : 4, mi = (deep % 100) / 10, st = deep % 10;
-    DRAG_CHECK((deep >= 400 && deep <= 405) || ((mi >= 1 && mi <= 4) && st >= 2 && st <= 4), "drag_gemm_bf16: gemm_kernel must be 0, 1, 2, 10 * MI + ST or 100 + 10 * MI + ST of a gemm_bf16_deep<MI, ST, NI> that is built");
-    tiles_of(deep >= 400 ? 256 : 32 * mi); k.tiles_n = (a->N + 32 * ni - 1) / (32 * ni);
-    const dim3 g(k.tiles_m * k.tiles_n);
-#define DRAG_DEEP_LAUNCH(MI_, ST_, NI_)                                                                                    \
-  {                                                                                                                        \
-    constexpr int lds = ST_ * (32 * MI_ + 32 * NI_) * 128;                                                                 \
-    static unsigned long long ready = 0;        /* one bit per device: the attribute belongs to the device's copy of the kernel */ \
-    int dev_ = 0;                                                                                                          \
-    (void)hipGetDevice(&dev_);                                                                                             \
-    if (!((ready >> (dev_ & 63)) & 1ull)) {                                                                                \
-      DRAG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_deep<MI_, ST_, NI_>),                       \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess,                      \
-                 "drag_gemm_bf16: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");                               \
-      ready |= 1ull << (dev_ & 63);                                                                                        \
-    }                                                                                                                      \
-    hipLaunchKernelGGL((gemm_bf16_deep<MI_, ST_, NI_>), g, dim3(256), lds, st_, k);                                       \
-  }                                                                                                                        \
-  break
-#define DRAG_DEEP(MI_, ST_) case 10 * MI_ + ST_: DRAG_DEEP_LAUNCH(MI_, ST_, 4)
-#define DRAG_DEEP6(MI_, ST_) case 100 + 10 * MI_ + ST_: DRAG_DEEP_LAUNCH(MI_, ST_, 6)
-#if DRAG_EXP
-    if (deep >= 400 && deep <= 405) {            // round-5 experiment: gemm_bf16_w4<variant>
-      DRAG_CHECK(a->K % 128 == 0 && a->K >= 256 && b == nullptr, "drag_gemm_bf16: gemm_kernel 400 (gemm_bf16_w4) needs K % 128 == 0, K >= 256, one segment");
-      k.tiles_m = (a->M + 255) / 256; k.tiles_n = (a->N + 255) / 256;
-      const dim3 g4(k.tiles_m * k.tiles_n);
-#define DRAG_W4(V_) case 400 + V_: DRAG_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_w4<V_>), hipFuncAttributeMaxDynamicSharedMemorySize, 131072) == hipSuccess, "hipFuncSetAttribute"); \
-      hipLaunchKernelGGL((gemm_bf16_w4<V_>), g4, dim3(256), 131072, st_, k); break
-      switch (deep) { DRAG_W4(0); DRAG_W4(1); DRAG_W4(2); DRAG_W4(3); DRAG_W4(4); DRAG_W4(5); default: DRAG_CHECK(false, "drag_gemm_bf16: gemm_kernel 400..405"); }
-#undef DRAG_W4
-      DRAG_LAUNCH_CHECK();
-      return 0;
-    }
-#endif
-    switch (deep) {
-      DRAG_DEEP(4, 2); DRAG_DEEP(4, 3);
-      DRAG_DEEP(3, 2); DRAG_DEEP(3, 3);
-      DRAG_DEEP(2, 2); DRAG_DEEP(2, 3); DRAG_DEEP(2, 4);
-      DRAG_DEEP(1, 3); DRAG_DEEP(1, 4);
-      DRAG_DEEP6(1, 3); DRAG_DEEP6(2, 3); DRAG_DEEP6(3, 3); DRAG_DEEP6(4, 3);
-      DRAG_DEEP6(3, 2); DRAG_DEEP6(4, 2); DRAG_DEEP6(3, 4); DRAG_DEEP6(4, 4);
-      default: DRAG_CHECK(false, "drag_gemm_bf16: gemm_kernel names a gemm_bf16_deep<MI, ST, NI> that is not built (42 43 32 33 22 23 24 13 14 | 113 123 133 143 132 142 134 144)");
-    }
-#undef DRAG_DEEP
-#undef DRAG_DEEP6
-#undef DRAG_DEEP_LAUNCH
-  } else {
-    tiles_of(BM); k.tiles_n = (a->N + BN - 1) / BN;
-    hipLaunchKernelGGL(gemm_bf16_t128<0>, dim3(k.tiles_m * k.tiles_n), dim3(256), 0, st_, k);
+  const KernelRow* row = kernel_row(choice);
+  if (row == nullptr) {
+    char msg[512];
+    size_t n = (size_t)snprintf(msg, sizeof(msg), "drag_gemm_bf16: gemm_kernel names a kernel that is not built (built, as drag_gemm_bf16_kernel_code lists them:");
+    for (int i = 0; i < kernel_rows && n < sizeof(msg); ++i) n += (size_t)snprintf(msg + n, sizeof(msg) - n, " %d", kernel_table[i].code);
+    if (n < sizeof(msg)) snprintf(msg + n, sizeof(msg) - n, ")");
+    drag_set_error(msg);
+    return -1;
   }
-  DRAG_LAUNCH_CHECK();
-  return 0;
+  if (choice >= 400)            // round-5 experiment: gemm_bf16_w4<variant>
+    DRAG_CHECK(a->K % 128 == 0 && a->K >= 256 && b == nullptr, "drag_gemm_bf16: gemm_kernel 400 (gemm_bf16_w4) needs K % 128 == 0, K >= 256, one segment");
+  // the 4-wave persistent kernel's own tile walk (profiles/r05_gemm_w4p_group_m.log, interleaved, TFLOP/s at g = 2 | 4 | 8): (42 696, 21 504, 3072)
+  // 1468 | 1449 | 1419, (32 768, 9216, 3072) 1473 | 1497 | 1481, (32 768, 3072, 12 288) 1520 | 1528 | 1513, (32 768, 3072, 3072) 1456 | 1423 | 1451
+  if (choice == 3 && drag_opt(DRAG_OPT_GEMM_GROUP_M) <= 0) k.group_m = a->N >= 16384 ? 2 : (a->N <= 3072 && a->K < 8192 ? 8 : 4);
+  k.tiles_m = (a->M + row->tm - 1) / row->tm;            // each segment starts on a tile boundary
+  if (b) { k.seg_tiles_m = k.tiles_m; k.tiles_m += (b->M + row->tm - 1) / row->tm; }
+  k.tiles_n = (a->N + row->tn - 1) / row->tn;
+  return launch_row(*row, b && row->form[FORM_PAIR].launch ? FORM_PAIR : FORM_ROWS, k, stream);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -523,16 +511,12 @@ extern "C" int drag_conv3x3_bf16(const drag_conv_args* a, void* stream) {
   GemmKArgs k;
   const long long M = (long long)a->B * a->Ho * a->Wo;
   DRAG_CHECK(M < (1ll << 31), "drag_conv3x3_bf16: too many output pixels");
-  const int grid = fill_common(k, a->x, a->w, a->y, a->bias, nullptr, a->resid, (int)M, a->Cout, 9 * a->Cin, a->ldy, 0, 0,
-                               0, a->act, 0, 0);
+  fill_common(k, a->x, a->w, a->y, a->bias, nullptr, a->resid, (int)M, a->Cout, 9 * a->Cin, a->ldy, 0, 0,
+              0, a->act, 0, 0);
   k.am.rpb = (int)M; k.am.bs = 0; k.am.ld = a->Cin;
   k.cv = ConvMap{a->Ho, a->Wo, a->Hp, a->Wp, a->Cin, a->stride, a->oy, a->ox};
   DRAG_CHECK(((long long)(BM * a->stride + 3 * a->Wp * 2) * a->Cin) * 2 < (1ll << 30), "drag_conv3x3_bf16: tile span too large");
-  if (use_t256(M, 0, a->Cout, 9 * a->Cin)) {
-    k.tiles_m = (int)((M + 255) / 256); k.tiles_n = (a->Cout + 255) / 256;
-    hipLaunchKernelGGL(gemm_bf16_t256<1>, dim3(t256_grid(k.tiles_m * k.tiles_n)), dim3(512), 0, (hipStream_t)stream, k);
-  } else
-    hipLaunchKernelGGL(gemm_bf16_t128<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, k);
-  DRAG_LAUNCH_CHECK();
-  return 0;
+  const KernelRow& row = *kernel_row(drag_conv3x3_bf16_choice(M, a->Cout, a->Cin));
+  k.tiles_m = (int)((M + row.tm - 1) / row.tm); k.tiles_n = (a->Cout + row.tn - 1) / row.tn;
+  return launch_row(row, FORM_CONV, k, stream);
 }

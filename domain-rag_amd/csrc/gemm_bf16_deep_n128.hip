@@ -3,14 +3,6 @@
 
 namespace drag_gemm {
 
-template __global__ void gemm_bf16_deep<4, 2, 4>(GemmKArgs);
-template __global__ void gemm_bf16_deep<4, 3, 4>(GemmKArgs);
-template __global__ void gemm_bf16_deep<3, 2, 4>(GemmKArgs);
-template __global__ void gemm_bf16_deep<3, 3, 4>(GemmKArgs);
-template __global__ void gemm_bf16_deep<2, 2, 4>(GemmKArgs);
-template __global__ void gemm_bf16_deep<2, 3, 4>(GemmKArgs);
-template __global__ void gemm_bf16_deep<2, 4, 4>(GemmKArgs);
-template __global__ void gemm_bf16_deep<1, 3, 4>(GemmKArgs);
-template __global__ void gemm_bf16_deep<1, 4, 4>(GemmKArgs);
+DRAG_GEMM_DEEP_N128(DRAG_GEMM_DEEP_DEFINE)
 
 }  // namespace drag_gemm

@@ -3,9 +3,6 @@
 
 namespace drag_gemm {
 
-template __global__ void gemm_bf16_deep<1, 3, 6>(GemmKArgs);
-template __global__ void gemm_bf16_deep<2, 3, 6>(GemmKArgs);
-template __global__ void gemm_bf16_deep<3, 3, 6>(GemmKArgs);
-template __global__ void gemm_bf16_deep<4, 3, 6>(GemmKArgs);
+DRAG_GEMM_DEEP_N192A(DRAG_GEMM_DEEP_DEFINE)
 
 }  // namespace drag_gemm

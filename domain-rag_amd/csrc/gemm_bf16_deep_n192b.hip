@@ -3,9 +3,6 @@
 
 namespace drag_gemm {
 
-template __global__ void gemm_bf16_deep<3, 2, 6>(GemmKArgs);
-template __global__ void gemm_bf16_deep<4, 2, 6>(GemmKArgs);
-template __global__ void gemm_bf16_deep<3, 4, 6>(GemmKArgs);
-template __global__ void gemm_bf16_deep<4, 4, 6>(GemmKArgs);
+DRAG_GEMM_DEEP_N192B(DRAG_GEMM_DEEP_DEFINE)
 
 }  // namespace drag_gemm

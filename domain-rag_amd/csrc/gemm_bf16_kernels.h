@@ -676,26 +676,18 @@ extern template __global__ void gemm_bf16_t128<1>(GemmKArgs);
 
 template <int MI, int ST, int NI>
 __global__ __launch_bounds__(256, 2) void gemm_bf16_deep(GemmKArgs p);                        // gemm_bf16_deep.h, instantiated in:
-// gemm_bf16_deep_n128.hip
-extern template __global__ void gemm_bf16_deep<4, 2, 4>(GemmKArgs);
-extern template __global__ void gemm_bf16_deep<4, 3, 4>(GemmKArgs);
-extern template __global__ void gemm_bf16_deep<3, 2, 4>(GemmKArgs);
-extern template __global__ void gemm_bf16_deep<3, 3, 4>(GemmKArgs);
-extern template __global__ void gemm_bf16_deep<2, 2, 4>(GemmKArgs);
-extern template __global__ void gemm_bf16_deep<2, 3, 4>(GemmKArgs);
-extern template __global__ void gemm_bf16_deep<2, 4, 4>(GemmKArgs);
-extern template __global__ void gemm_bf16_deep<1, 3, 4>(GemmKArgs);
-extern template __global__ void gemm_bf16_deep<1, 4, 4>(GemmKArgs);
-// gemm_bf16_deep_n192a.hip
-extern template __global__ void gemm_bf16_deep<1, 3, 6>(GemmKArgs);
-extern template __global__ void gemm_bf16_deep<2, 3, 6>(GemmKArgs);
-extern template __global__ void gemm_bf16_deep<3, 3, 6>(GemmKArgs);
-extern template __global__ void gemm_bf16_deep<4, 3, 6>(GemmKArgs);
-// gemm_bf16_deep_n192b.hip
-extern template __global__ void gemm_bf16_deep<3, 2, 6>(GemmKArgs);
-extern template __global__ void gemm_bf16_deep<4, 2, 6>(GemmKArgs);
-extern template __global__ void gemm_bf16_deep<3, 4, 6>(GemmKArgs);
-extern template __global__ void gemm_bf16_deep<4, 4, 6>(GemmKArgs);
+// The ring forms X(MI, ST, NI), one list per instantiating source (three sources: the compile time is balanced between them).  The lists
+// are the only place a form is written: from them come the declarations below, each source's instantiations (DRAG_GEMM_DEEP_DEFINE) and
+// the host's table rows (gemm_bf16.hip), where a form's code is 100 * (NI == 6) + 10 * MI + ST.
+#define DRAG_GEMM_DEEP_N128(X) X(4, 2, 4) X(4, 3, 4) X(3, 2, 4) X(3, 3, 4) X(2, 2, 4) X(2, 3, 4) X(2, 4, 4) X(1, 3, 4) X(1, 4, 4)      // gemm_bf16_deep_n128.hip
+#define DRAG_GEMM_DEEP_N192A(X) X(1, 3, 6) X(2, 3, 6) X(3, 3, 6) X(4, 3, 6)                                                            // gemm_bf16_deep_n192a.hip
+#define DRAG_GEMM_DEEP_N192B(X) X(3, 2, 6) X(4, 2, 6) X(3, 4, 6) X(4, 4, 6)                                                            // gemm_bf16_deep_n192b.hip
+#define DRAG_GEMM_DEEP_DEFINE(MI_, ST_, NI_) template __global__ void gemm_bf16_deep<MI_, ST_, NI_>(GemmKArgs);
+#define DRAG_GEMM_DEEP_EXTERN(MI_, ST_, NI_) extern DRAG_GEMM_DEEP_DEFINE(MI_, ST_, NI_)
+DRAG_GEMM_DEEP_N128(DRAG_GEMM_DEEP_EXTERN)
+DRAG_GEMM_DEEP_N192A(DRAG_GEMM_DEEP_EXTERN)
+DRAG_GEMM_DEEP_N192B(DRAG_GEMM_DEEP_EXTERN)
+#undef DRAG_GEMM_DEEP_EXTERN
 
 template <int MODE>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_t256(GemmKArgs p);                        // gemm_bf16_t256.h, instantiated in gemm_bf16_t256.hip
@@ -707,12 +699,11 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_w4p(GemmKArgs p);           
 #if DRAG_EXP
 template <int V>
 __global__ __launch_bounds__(256, 1) void gemm_bf16_w4(GemmKArgs p);
-extern template __global__ void gemm_bf16_w4<0>(GemmKArgs);
-extern template __global__ void gemm_bf16_w4<1>(GemmKArgs);
-extern template __global__ void gemm_bf16_w4<2>(GemmKArgs);
-extern template __global__ void gemm_bf16_w4<3>(GemmKArgs);
-extern template __global__ void gemm_bf16_w4<4>(GemmKArgs);
-extern template __global__ void gemm_bf16_w4<5>(GemmKArgs);
+#define DRAG_GEMM_W4_VARIANTS(X) X(0) X(1) X(2) X(3) X(4) X(5)      // "gemm_kernel" = 400 + V
+#define DRAG_GEMM_W4_DEFINE(V_) template __global__ void gemm_bf16_w4<V_>(GemmKArgs);
+#define DRAG_GEMM_W4_EXTERN(V_) extern DRAG_GEMM_W4_DEFINE(V_)
+DRAG_GEMM_W4_VARIANTS(DRAG_GEMM_W4_EXTERN)
+#undef DRAG_GEMM_W4_EXTERN
 #endif
 
 }  // namespace drag_gemm

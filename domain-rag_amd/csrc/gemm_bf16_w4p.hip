@@ -280,12 +280,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_w4p(GemmKArgs p) {
 }
 
 #if DRAG_EXP
-template __global__ void gemm_bf16_w4<0>(GemmKArgs);
-template __global__ void gemm_bf16_w4<1>(GemmKArgs);
-template __global__ void gemm_bf16_w4<2>(GemmKArgs);
-template __global__ void gemm_bf16_w4<3>(GemmKArgs);
-template __global__ void gemm_bf16_w4<4>(GemmKArgs);
-template __global__ void gemm_bf16_w4<5>(GemmKArgs);
+DRAG_GEMM_W4_VARIANTS(DRAG_GEMM_W4_DEFINE)
 #endif
 
 }  // namespace drag_gemm

@@ -18,7 +18,7 @@
 //                          component plane.
 //   jpeg_color_kernel      one thread per output pixel: fancy chroma upsampling + YCbCr -> RGB, 3-byte store.
 // The last two are plain data-parallel integer kernels bound by the load/store units (no reuse to stage in LDS).
-#include "drag_common.h"
+#include "drag_launch.h"
 #include "jpeg_core.h"
 #include "jpeg_internal.h"
 
@@ -286,24 +286,9 @@ extern "C" int drag_jpeg_decode_rgb(const void* data, const int64_t* offsets, co
 // the lane kernels (sequential files the mask names — all of them without a mask — and progressive files), then IDCT and colour
 int jpeg_lane_and_pixels(const JpegArgs& a, int64_t max_blocks, int64_t max_pixels, hipStream_t st) {
   const int n = a.n;
-  hipError_t e;
   const int lds = JPEG_HUFF_LDS;                                          // 85 KiB per wave
-  static bool lds_ok = false;
-  if (!lds_ok) {
-    e = hipFuncSetAttribute((const void*)jpeg_huffman_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    DRAG_CHECK(e == hipSuccess, "drag_jpeg_decode_rgb: cannot raise the dynamic LDS limit to 128 KiB");
-    lds_ok = true;
-  }
-  hipLaunchKernelGGL(jpeg_huffman_kernel, dim3((n + 63) / 64), dim3(64), lds, st, a);
-  DRAG_LAUNCH_CHECK();
-  static bool lds_ok2 = false;
-  if (!lds_ok2) {
-    e = hipFuncSetAttribute((const void*)jpeg_progressive_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    DRAG_CHECK(e == hipSuccess, "drag_jpeg_decode_rgb: cannot raise the dynamic LDS limit (progressive kernel)");
-    lds_ok2 = true;
-  }
-  hipLaunchKernelGGL(jpeg_progressive_kernel, dim3((n + 63) / 64), dim3(64), lds, st, a);     // SOF2 files; other lanes leave at once
-  DRAG_LAUNCH_CHECK();
+  if (int rc = drag_launch<jpeg_huffman_kernel>(dim3((n + 63) / 64), 64, lds, st, a)) return rc;
+  if (int rc = drag_launch<jpeg_progressive_kernel>(dim3((n + 63) / 64), 64, lds, st, a)) return rc;     // SOF2 files; other lanes leave at once
   hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + 255) / 256), n), dim3(256), 0, st, a);
   DRAG_LAUNCH_CHECK();
   hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((max_pixels + 255) / 256), n), dim3(256), 0, st, a);

@@ -40,7 +40,7 @@
 // (SCAN_SCORES_GMAX), select_groups_kernel takes the k-th best group maximum as the bound — exactly k groups reach it and the answer
 // lives in their 16 k rows — gathers those scores and ranks them.  No sample, no threshold launch, no candidate regions; the work does
 // not depend on the score distribution.  Q = 1 call at N = 118 287: 61.5 -> 47.2 us for a 37.7 us scan.
-#include "drag_common.h"
+#include "drag_launch.h"
 #include <float.h>
 
 namespace {
@@ -903,13 +903,7 @@ inline int scan_grid(long long niter, int ntile) {
 template <int NBUF, int QT>
 int launch_scan_n(ScanArgs& sa, hipStream_t st) {
   const int lds = QT * (sa.d / 64) * 4096 + 4 * NBUF * 4096;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)ip_scan_kernel<NBUF, QT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    DRAG_CHECK(e == hipSuccess, "cosine scan: cannot raise dynamic LDS limit");
-  }
-  hipLaunchKernelGGL((ip_scan_kernel<NBUF, QT>), dim3(scan_grid(sa.niter, sa.ntile)), dim3(256), lds, st, sa);
-  DRAG_LAUNCH_CHECK();
-  return 0;
+  return drag_launch<ip_scan_kernel<NBUF, QT>>(dim3(scan_grid(sa.niter, sa.ntile)), 256, lds, st, sa);      // (d >= 768: more than 64 KiB)
 }
 // Query tiles per workgroup ("topk_qt"; 0 = the default, 1): 1 — every tile of 16 queries gets its own workgroup and the tiles of a
 // row range share the corpus through their XCD's L2 (two workgroups per CU); 2 / 4 — a workgroup keeps that many tiles in LDS and

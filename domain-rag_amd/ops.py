@@ -50,17 +50,16 @@ class GemmRecorder:
         if isinstance(conv, tuple) and conv[0] == "splitk":  # drag_gemm_bf16 as stacked K slices + the reduce pass (one recorded interval)
             return "gemm_bf16_w4p + splitk_reduce_kernel"
         M1, M2 = (conv[1], conv[2]) if isinstance(conv, tuple) else (M, 0)
+        lib = _lib.load()
         if conv is True:                                     # the 3x3 convolutions take t256 or t128 only, by their own predicate
-            return "gemm_bf16_t256<1>" if _lib.load().drag_conv3x3_bf16_choice(M, N, K // 9) == 2 else "gemm_bf16_t128<1>"
-        code = _lib.load().drag_gemm_bf16_choice(M1, M2, N, K)
-        if code == 3:
-            return "gemm_bf16_w4p"
-        if code == 2:
-            return "gemm_bf16_t256_pair" if M2 > 0 else "gemm_bf16_t256<0>"
-        if code == 0:
-            return "gemm_bf16_t128<0>"
-        mi, st = (code % 100) // 10, code % 10
-        return f"gemm_bf16_deep<{mi}, {st}, 6>" if code >= 100 else f"gemm_bf16_deep<{mi}, {st}>"
+            code, form = lib.drag_conv3x3_bf16_choice(M, N, K // 9), 2
+        else:
+            code, form = lib.drag_gemm_bf16_choice(M1, M2, N, K), int(M2 > 0)
+        # the name from the library's kernel table; a merged pair runs the rows kernel where the code has no pair kernel of its own
+        name = lib.drag_gemm_bf16_kernel_name(code, form) or lib.drag_gemm_bf16_kernel_name(code, 0)
+        if name is None:
+            raise RuntimeError(f"gemm kernel code {code} is not built (drag_gemm_bf16_kernel_code enumerates the codes that are)")
+        return name.decode()
 
     def by_kernel(self):
         """{kernel name: (launches, total_ms, flops)}"""
@@ -213,17 +212,12 @@ def _recorded(call, shape, kind=False):
 
 def _recorded_attention(call, B, S, H, qprep, vrow):
     """run one head_dim-128 attention launch, bracketed by events when a recorder is installed (4 S^2 128 flops per batch and head:
-    q k^T and p v; the kernel name from the library's own dispatch, ``drag_attention_bf16_choice``)"""
+    q k^T and p v; the kernel name from the library's own dispatch, ``drag_attention_bf16_kernel_name``)"""
     if _recorder is None:
         call()
         return
     # the name before the launch: what the launch is about to read is what gets reported
-    fam = _lib.load().drag_attention_bf16_choice(S, int(vrow), int(qprep))
-    q = "true" if qprep else "false"
-    gen = get_option("attn_gen")
-    variant = f", {gen - 10}" if experiments_built() and 11 <= gen <= 29 else ""     # experiment builds: the generated stream's schedule variants
-    name = {64: f"attention_q64_kernel<{q}>", 640: f"attention_q64g_kernel<{q}, false>", 641: f"attention_q64g_kernel<{q}, true{variant}>"}.get(
-        fam, f"attention_d128_kernel<{fam}, ..., {q}, ...>")
+    name = _lib.load().drag_attention_bf16_kernel_name(S, int(vrow), int(qprep)).decode()
     s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s_ev.record()
     call()

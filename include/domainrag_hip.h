@@ -38,8 +38,8 @@ const char* drag_last_error(void);
  *                                         the scale folded into the fused q preparation (its own, equally accurate rounding) | the hand-placed
  *                                         kernel | the generated stream without the fold (the hand-placed kernel's bits); 11..29 select
  *                                         schedule variants in experiment builds
- *   "gemm_kernel"         0 | code        tile policy | 1 = 128x128, 2 = 256x256 (8 waves), 3 = 256x256 (4 waves), from 10 on the ring kernels'
- *                                         codes as drag_gemm_bf16_choice reports them (400 / 401: experiment builds only)
+ *   "gemm_kernel"         0 | code        tile policy | 1 = the 128x128 kernel, else one of the codes drag_gemm_bf16_kernel_code enumerates
+ *                                         (drag_gemm_bf16_kernel_name tells the kernel; a code that is not built is refused at the launch)
  *   "gemm_t128"           0 | 1           withdraw the 256x256 kernels from the tile policy and leave the rest to it (not "gemm_kernel" = 1)
  *   "gemm_no_96"          0 | 1           withdraw the 96-row tiles from the tile policy
  *   "gemm_no_192"         0 | 1           withdraw the 192-column tiles from the tile policy
@@ -134,6 +134,13 @@ int drag_gemm_bf16_pair_merges(int M1, int M2, int N, int K);
  * kernel, 0 = the 128x128 kernel, else 100 * (192-column tiles) + 10 * MI + ST of gemm_bf16_deep<MI, ST, NI>.  Every choice computes the
  * same bits; the policy is a function of the launch shape only. */
 int drag_gemm_bf16_choice(int M1, int M2, int N, int K);
+/* The kernels behind those codes, from the library's one table of them.  drag_gemm_bf16_kernel_code(i) enumerates the codes that are
+ * built (-1 past the end); these, and 1 for the 128x128 kernel, are the values "gemm_kernel" takes.  drag_gemm_bf16_kernel_name(code, form)
+ * is the kernel's name the way a profiler prints it ("gemm_bf16_t256<0>", "gemm_bf16_deep<4, 3>", "gemm_bf16_deep<3, 3, 6>"): form 0 = the
+ * kernel of drag_gemm_bf16, 1 = the kernel of a merged drag_gemm_bf16_pair launch where that is a kernel of its own ("gemm_bf16_t256_pair";
+ * NULL where the form-0 kernel runs the pair too), 2 = the kernel of drag_conv3x3_bf16; NULL for a code or form that is not built. */
+int32_t drag_gemm_bf16_kernel_code(int32_t index);
+const char* drag_gemm_bf16_kernel_name(int32_t code, int32_t form);
 /* the kernel drag_conv3x3_bf16 dispatches M = B*Ho*Wo output pixels x Cout x (9*Cin) to: 2 = the 256x256 kernel, 0 = the 128x128 one */
 int drag_conv3x3_bf16_choice(int64_t M, int Cout, int Cin);
 /* the policy's cost model for that launch: (tile rounds on the busiest CU) x (tile rows + tile columns), i.e. proportional to what the
@@ -259,6 +266,10 @@ int drag_attention_v_bf16(const void* q, const void* k, const void* v, void* out
  * A pure query (no launch) for callers that account launches per kernel — bench.py's roofline.attention; nothing in the reference
  * corresponds (SDPA picks its backend inside torch). */
 int drag_attention_bf16_choice(int32_t S, int32_t v_row_major, int32_t q_prep);
+/* The same decision as the kernel's name, the way a profiler prints it: "attention_q64g_kernel<true, true>" (", V" appended for a schedule
+ * variant of an experiment build's "attn_gen" 11..29), "attention_q64_kernel<false>", "attention_d128_kernel<8, ..., true, ...>" (waves and
+ * q preparation only).  What the NEXT launch of that shape takes under the current switches: ask before the launch.  A pure query. */
+const char* drag_attention_bf16_kernel_name(int32_t S, int32_t v_row_major, int32_t q_prep);
 
 /* drag_layernorm_modulate_bf16 — y = LN(x) * (1 + scale[b]) + shift[b]   (no affine LN, eps given)
  * or, with gamma/beta != NULL, y = LN(x) * gamma + beta (affine LayerNorm, scale/shift NULL).

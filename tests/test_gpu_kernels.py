@@ -859,7 +859,7 @@ def test_gemm_kernels_are_bit_identical(gpu, M, N, K):
     """every GEMM kernel (t128, t256, gemm_bf16_deep<MI, ST, NI>: 128- and 192-column tiles) runs the same MFMA in the same k order per output element, so
     the tile policy may depend on the launch's shape without changing a bit: plain, activation, gate + residual in batched
     rows, f32 output and the narrow (fragment) epilogue"""
-    from domain_rag_amd import ops
+    from domain_rag_amd import _lib, ops
     a, w, b = _randn((M, K), 1).to(gpu), _randn((N, K), 2, 0.05).to(gpu), _randn((N,), 3).to(gpu)
     rpb = M // 2 if M % 2 == 0 else M
     nb = M // rpb
@@ -876,7 +876,12 @@ def test_gemm_kernels_are_bit_identical(gpu, M, N, K):
         outs.append(y)
         return [o.cpu() for o in outs]
 
-    codes = [1, 42, 43, 32, 33, 22, 23, 24, 13, 14, 113, 123, 133, 143, 132, 142, 134, 144, 0] + ([2, 3] if N >= 256 and K >= 256 else [])      # 1xx: 192-column tiles; 3: the 4-wave persistent kernel (where K % 128 == 0, else the 8-wave one)
+    lib, ring = _lib.load(), []      # the ring kernels' codes from the library's table (tests/test_kernel_tables.py pins the set); 1xx: 192-column tiles
+    while (c := lib.drag_gemm_bf16_kernel_code(len(ring))) >= 0:
+        ring.append(c)
+    ring = [c for c in ring if 10 <= c < 400]
+    assert len(ring) >= 17
+    codes = [1] + ring + [0] + ([2, 3] if N >= 256 and K >= 256 else [])      # 3: the 4-wave persistent kernel (where K % 128 == 0, else the 8-wave one)
     res = {}
     for code in codes:
         with ops.options(gemm_kernel=code):
