@@ -137,6 +137,12 @@ SIGNATURES = {
                                  + [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "drag_png_plan": (c_int, [c_int] * 4 + [c_void_p, c_void_p]),
     "drag_png_encode": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "drag_png_decode_geometry": (c_int, [c_void_p] * 4),
+    "drag_png_parse_workspace": (c_int, [c_int, c_int64, c_void_p]),
+    "drag_png_parse": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "drag_png_decode_plan": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "drag_png_decode": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64,
+                                c_void_p, c_void_p]),
     "drag_jpeg_encode_plan": (c_int, [c_int] * 5 + [c_void_p, c_void_p]),
     "drag_jpeg_encode": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
 }

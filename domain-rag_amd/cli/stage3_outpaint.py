@@ -32,6 +32,15 @@ from ..io_pool import ImageWriter
 RESULT_DIR, DATASETS_DIR = "./result", "./datasets"
 
 
+# --pictures: who opens the backgrounds and resizes the results back.  Both settings write byte-identical files
+# (tests/test_gpu_stage3_pictures.py).  The rule is stage0_lama.SOURCE_DEFAULT's: "device" only if stage 3's per-sample wall clock with it
+# is not above "host"'s in the same run.  Measured on an MI355X (scripts/bench_stage3_pictures.py, profiles/stage3_pictures.log: the tiny
+# engine, 4 samples of 5 backgrounds of 1024 x 1024 written by the GPU encoder, 2 steps, 4 counted alternating passes in one process):
+# 34.0 ms per sample on "device" (33.6 ... 35.2) against 74.6 ms on "host" (74.0 ... 75.2), every device sample below every host sample.
+# A full-size run (real weights, seconds per sample) has not been measured; what the device route saves there is the same few tens of ms.
+PICTURES_DEFAULT = "device"
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="高分辨率Outpainting处理脚本 (MI355X)")
     p.add_argument("--dataset", type=str)
@@ -66,6 +75,9 @@ def build_parser():
     p.add_argument("--png", choices=["gpu", "host"], default="gpu",
                    help="*_hires_result_* / *_final_result_*: 'gpu' = encoded on the device (domain_rag_amd.png: same pixels, not "
                         "Pillow's bytes), 'host' = Pillow (zlib level 6) in the --io_workers processes; masks and copies stay with Pillow")
+    p.add_argument("--pictures", choices=["device", "host"], default=PICTURES_DEFAULT,
+                   help="device: the generated_image*.png backgrounds are decoded on the device (domain_rag_amd.png.decode_paths; files it "
+                        "declines go through Pillow as before) and, with --png gpu, the results are resized back there too; host: Pillow")
     p.add_argument("--bg_batch", type=int, default=8, help="backgrounds of one sample composited per batch (1 = one at a time like the reference)")
     return p
 
@@ -166,25 +178,38 @@ def process_sample(engine: Engine, args, dataset, sample_id, sample_dir, shot, p
         msk_u8 = torch.from_numpy(np.asarray(mk16, dtype=np.uint8).copy())[None].to(engine.dev)
         # ---- backgrounds of one sample share image, mask and size: they are generated as ONE batch (each with its own
         # seed / generator draws and its own Redux prior), which is ~8 % faster per composite than one at a time
+        pictures = getattr(args, "pictures", PICTURES_DEFAULT)
+        dec = None
+        if pictures == "device":                      # all backgrounds of the sample in one call; what the device declines is opened below as ever
+            from .. import png as png_dec
+            try:
+                dec = png_dec.decode_paths(bgs, engine.dev)
+                n_dev = sum(r == "device" for r in dec.route)
+                print(f"样本 {sample_id} 背景解码: device {n_dev}, pil {len(bgs) - n_dev}")
+            except Exception as e:
+                print(f"样本 {sample_id} 背景解码 (device) 失败, 改用 Pillow: {str(e)}")
         jobs = []
         for bg_idx, bg_path in enumerate(bgs):
             name = os.path.basename(bg_path)
             suffix = f"_{name.split('rank')[1].split('.')[0]}" if "rank" in name else f"_{bg_idx + 1}"
             mask_path = os.path.join(out_dir, f"{prefix}_mask{suffix}.png")
             mask_img.save(mask_path)
-            try:
-                bg = H.load_image_rgb(bg_path)
-            except Exception as e:
-                print(f"加载背景图像 {bg_path} 失败: {str(e)}")
-                continue
+            bg, bg_dev = None, (dec.images[bg_idx] if dec is not None and dec.route[bg_idx] == "device" else None)
+            if bg_dev is None:
+                try:
+                    bg = H.load_image_rgb(bg_path)
+                except Exception as e:
+                    print(f"加载背景图像 {bg_path} 失败: {str(e)}")
+                    continue
             bg_saved = os.path.join(out_dir, f"{prefix}_bg{suffix}_original.png")
             shutil.copy(bg_path, bg_saved)
-            jobs.append(dict(bg_idx=bg_idx, bg_path=bg_path, name=name, suffix=suffix, mask_path=mask_path, bg=bg, bg_saved=bg_saved,
+            jobs.append(dict(bg_idx=bg_idx, bg_path=bg_path, name=name, suffix=suffix, mask_path=mask_path, bg=bg, bg_dev=bg_dev, bg_saved=bg_saved,
                              seed=rng.randint(0, 2 ** 32 - 1)))
         for c0 in range(0, len(jobs), max(1, args.bg_batch)):
             chunk = jobs[c0:c0 + max(1, args.bg_batch)]
             n = len(chunk)
-            priors = [engine.prior_embeds([jb["bg"]], prompt, [ips], [1.0]) for jb in chunk]
+            priors = [engine.prior_embeds_device([jb["bg_dev"]], prompt, [ips], [1.0]) if jb["bg_dev"] is not None
+                      else engine.prior_embeds([jb["bg"]], prompt, [ips], [1.0]) for jb in chunk]
             pe, pp = torch.cat([a for a, _ in priors], 0), torch.cat([b for _, b in priors], 0)
             draws = [generator_noise(jb["seed"], 1, H16, W16, 3) for jb in chunk]      # per image: enc, noise, masked-enc (pipeline order)
             enc_n = torch.cat([d[0] for d in draws], 0)
@@ -198,17 +223,29 @@ def process_sample(engine: Engine, args, dataset, sample_id, sample_dir, shot, p
             if getattr(args, "png", "host") == "gpu":
                 from .. import png as gpu_png
                 hires_files = gpu_png.encode(outs_dev)
-            outs = outs_dev.cpu().numpy()
+            final_files = None
+            if gpu_png is not None and pictures == "device":
+                # the resize back to the original resolution on the device too (resample.resize_u8: Pillow's BICUBIC, bit for bit): no copy
+                # of the results to the host on this route
+                from .. import resample
+                back = H.resize_back_size(W16, H16, up, down, wu, wd)
+                final_files = hires_files if back is None or back == (W16, H16) else gpu_png.encode(resample.resize_u8(outs_dev, back[0], back[1], "bicubic"))
+                outs = [None] * n
+            else:
+                outs = outs_dev.cpu().numpy()
             for k_out, (jb, arr) in enumerate(zip(chunk, outs)):
                 bg_idx, bg_path, name, suffix, mask_path, bg_saved, seed = (jb[k] for k in ("bg_idx", "bg_path", "name", "suffix", "mask_path", "bg_saved", "seed"))
-                result = Image.fromarray(arr)
                 hires_path = os.path.join(out_dir, f"{prefix}_hires_result{suffix}.png")
-                final = H.downscale_image(result, up) if wu else (H.upscale_image(result, 1.0 / down) if wd else result)
                 final_path = os.path.join(out_dir, f"{prefix}_final_result{suffix}.png")
+                if final_files is None:
+                    result = Image.fromarray(arr)
+                    final = H.downscale_image(result, up) if wu else (H.upscale_image(result, 1.0 / down) if wd else result)
                 if gpu_png is not None:
                     with open(hires_path, "wb") as f:
                         f.write(hires_files[k_out])
-                    if final is result:
+                    if final_files is not None:
+                        final_file = final_files[k_out]
+                    elif final is result:
                         final_file = hires_files[k_out]
                     else:                     # the resize back to the original resolution is the host's (PIL); its pixels go up once
                         final_file = gpu_png.encode(torch.from_numpy(np.array(final.convert("RGB"))).to(engine.dev))[0]

@@ -245,3 +245,16 @@ class Engine:
         t5, pooled = self.text.get(prompt, "")
         imgs = siglip_input_device(pil_images, self.vit_cfg.image_size, self.dev)
         return self.prior(imgs, t5, pooled, embeds_scale, pooled_scale, group=len(pil_images))
+
+    def prior_embeds_device(self, images_u8, prompt: str, embeds_scale, pooled_scale):
+        """``prior_embeds`` for pictures that are already on the device (uint8 [H, W, 3] each, e.g. ``png.decode_files``' images): the same
+        ``siglip_resize_u8`` kernel on the same bytes as ``siglip_input_device``, minus the upload — the same bits"""
+        from . import resample
+        t5, pooled = self.text.get(prompt, "")
+        size = self.vit_cfg.image_size
+        imgs = torch.empty((len(images_u8), size, size, 3), dtype=torch.uint8, device=self.dev)
+        for i, raw in enumerate(images_u8):
+            if raw.dtype != torch.uint8 or raw.dim() != 3 or raw.shape[-1] != 3 or raw.device != self.dev:
+                raise ValueError("prior_embeds_device: uint8 [H, W, 3] tensors on the engine's device expected")
+            resample.siglip_resize_u8(raw.contiguous(), size, out=imgs[i])
+        return self.prior(imgs, t5, pooled, embeds_scale, pooled_scale, group=len(images_u8))

@@ -554,6 +554,38 @@ int drag_png_plan(int32_t n, int32_t H, int32_t W, int32_t C, int64_t* workspace
 int drag_png_encode(const void* images, int32_t n, int32_t H, int32_t W, int32_t C, void* workspace, int64_t workspace_bytes,
                     void* out, int64_t out_stride, int64_t* sizes, void* stream);
 
+/* PNG files in HBM -> uint8 pixels in HBM, exactly PIL's `Image.open(f).convert("RGB")` / `"L"`, for the class of files
+ * drag_png_encode writes: 8-bit grey / RGB, not interlaced, ONE final dynamic-Huffman DEFLATE block whose header says HLIT = 257
+ * (no length symbols exist, so the absence of LZ77 matches is proved).  One file is decoded by many lanes (subsequences of the
+ * compressed bytes + Jacobi rounds, csrc/png_dec_core.h); every other file gets a status and is left to the caller.
+ *   drag_png_decode_geometry: bytes per subsequence, subsequences per workgroup, round cap, rows per un-filter band.
+ *   drag_png_parse_workspace: bytes of the parse workspace for n files of total_bytes together.
+ *   drag_png_parse:  data = the files back to back, file i = [offsets[i], offsets[i + 1]) (device int64 [n + 1], offsets[n] <=
+ *                    total_bytes).  Walks the chunks (CRC-32 of every chunk), gathers the IDAT payloads, reads the zlib and block
+ *                    headers, builds the code table -> info int32 [n, 16] (device): status, width, height, channels, IDAT bytes,
+ *                    first data bit, end bit, subsequences, Adler-32, IDAT chunks.  parse_ws keeps what drag_png_decode needs.
+ *   drag_png_decode_plan (host only): info read back -> plan int64 [n, 4] (first subsequence slot, filtered-byte offset, output
+ *                    offset, output bytes; zeros for a declined file), totals int64 [5] (subsequences, filtered bytes, output
+ *                    bytes, most subsequences in one file, most filtered bytes in one file), workspace bytes.
+ *   drag_png_decode: info and plan on the device, totals on the host.  File i's pixels ([H, W, C], or [H, W, 3] for a grey file
+ *                    when want_rgb) at out + plan[i][2], written ONLY when stats[i][0] == 0.  stats int32 [n, 4] (device): status,
+ *                    fallback reason, rounds, subsequences.  Workspaces 256-byte aligned.  Everything is enqueued on `stream`.
+ * status: 0 decoded; 1 not a PNG; 2 truncated; 3 chunk CRC; 4 bit depth; 5 colour type / palette / alpha; 6 interlaced;
+ *   7 stored / fixed / multi-block; 8 HLIT > 257; 9 bad code table; 10 eXIf; 11 too large; 12 other (zlib header, unknown critical
+ *   or APNG chunk, IDATs not consecutive, more than 8192 chunks); 13 Adler-32 mismatch; 14 filter byte > 4; 15 fell back, reason:
+ *   1 a window that is no code; 2 a symbol needs bits past the stream (also: no end-of-block); 3 end-of-block too early; 4 data
+ *   between end-of-block and the Adler-32; 5 too many literals; 6 round cap.  10 also covers the text chunks Pillow reads an
+ *   orientation from ("Raw profile type exif", the XMP packet).  16 is never written by the library: png.py's decode_files puts it
+ *   into its copy of the descriptors when mode "L" is asked of an RGB file. */
+int drag_png_decode_geometry(int32_t* subsequence_bytes, int32_t* span, int32_t* round_cap, int32_t* band_rows);
+int drag_png_parse_workspace(int32_t n, int64_t total_bytes, int64_t* workspace_bytes);
+int drag_png_parse(const void* data, const int64_t* offsets, int32_t n, int64_t total_bytes, void* parse_ws, int64_t parse_ws_bytes,
+                   int32_t* info, void* stream);
+int drag_png_decode_plan(const int32_t* info, int32_t n, int32_t want_rgb, int64_t* plan, int64_t* totals, int64_t* workspace_bytes);
+int drag_png_decode(const void* parse_ws, const int64_t* offsets, int32_t n, int64_t total_bytes, const int32_t* info, const int64_t* plan,
+                    const int64_t* totals, int32_t want_rgb, void* workspace, int64_t workspace_bytes, void* out, int64_t out_bytes,
+                    int32_t* stats, void* stream);
+
 /* uint8 images in HBM -> complete baseline JPEG files in HBM, BYTE-IDENTICAL to what Pillow writes for `Image.save(path)` /
  * `Image.save(f, "JPEG", quality=q, subsampling=s)` (libjpeg's default path: fixed-point RGB -> YCbCr, box downsampling, ISLOW
  * forward DCT, Annex K quantisation tables scaled by the quality, Annex K Huffman tables, one interleaved scan, JFIF header);
