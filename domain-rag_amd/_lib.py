@@ -83,6 +83,9 @@ SIGNATURES = {
     "drag_attention_bf16_kernel_name": (ctypes.c_char_p, [c_int, c_int, c_int]),
     "drag_attention_v_bf16": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_int64, c_int, c_int64, c_float] + [c_void_p] * 4 + [c_int, c_float, c_void_p]),
     "drag_layernorm_modulate_bf16": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_int64, c_int, c_int, c_float, c_void_p]),
+    "drag_stepcache_workspace_bytes": (c_int64, [c_int] * 3),
+    "drag_stepcache_delta_bf16": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_int64, c_void_p]),
+    "drag_stepcache_apply_bf16": (c_int, [c_void_p, c_void_p] + [c_int] * 3 + [c_int64, c_int, c_void_p]),
     "drag_act_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "drag_timestep_embedding_bf16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "drag_flow_euler_step_bf16": (c_int, [c_void_p, c_void_p, c_float, c_int64, c_void_p]),

@@ -27,6 +27,7 @@ import torch
 
 from .. import hostlogic as H
 from ..engine import Engine, generator_noise, pack_noise
+from ..flux import parse_step_cache
 from ..io_pool import ImageWriter
 
 RESULT_DIR, DATASETS_DIR = "./result", "./datasets"
@@ -67,6 +68,10 @@ def build_parser():
     p.add_argument("--linear_precision", choices=["bf16", "mxfp8"], default=None,
                    help="the DiT blocks' Linears: bf16, or OCP MXFP8 operands on the block-scaled matrix instruction (opt-in, lower "
                         "precision); default: $DRAG_LINEAR_PRECISION, else bf16")
+    p.add_argument("--step_cache", type=parse_step_cache, default=None, metavar="THRESHOLD",
+                   help="first-block step cache of the denoise loop (opt-in, lower fidelity): a step whose first-block residual moved by less "
+                        "than THRESHOLD (relative L1, every image of the batch) since the last computed step reuses that step's remaining "
+                        "blocks; batch neighbours then influence a result (--bg_batch 1 restores independence); default: $DRAG_STEP_CACHE, else off")
     p.add_argument("--text_encoder", choices=["transformers", "hip"], default="transformers",
                    help="what encodes a prompt without a prompt_cache file: the transformers T5 / CLIP modules (eager torch) or the HIP "
                         "encoders (domain_rag_amd.textenc); tokenizers are host Python either way")
@@ -80,6 +85,11 @@ def build_parser():
                         "declines go through Pillow as before) and, with --png gpu, the results are resized back there too; host: Pillow")
     p.add_argument("--bg_batch", type=int, default=8, help="backgrounds of one sample composited per batch (1 = one at a time like the reference)")
     return p
+
+
+def step_cache_params(step_cache) -> dict:
+    """what a result's parameter JSON gains when the step cache is on; nothing when it is off (the file is then byte-identical)"""
+    return {"step_cache": step_cache} if step_cache else {}
 
 
 def dataset_result_dirs(result_dir, dataset, shot):
@@ -263,6 +273,7 @@ def process_sample(engine: Engine, args, dataset, sample_id, sample_dir, shot, p
                           "min_dimension_used": min_dim, "up_scale_factor": up, "down_scale_factor": down, "was_upscaled": wu,
                           "was_downscaled": wd, "bbox_coords_list": bboxes, "processed_bbox_coords_list": pb,
                           "image_id": info["id"] if info.get("id") is not None else "unknown", "num_bbox": len(bboxes)}
+                params.update(step_cache_params(getattr(engine.pipe, "step_cache", None)))
                 params_path = os.path.join(out_dir, f"{prefix}_params{suffix}.json")
                 with open(params_path, "w") as f:
                     json.dump(params, f, indent=2)
@@ -307,7 +318,7 @@ def run_rank(args, datasets, process_id, rank, world, gpu_process_id=None):
     local = int(os.environ.get("LOCAL_RANK", str(rank))) % max(torch.cuda.device_count(), 1)   # (more ranks than GPUs: share them)
     torch.cuda.set_device(local)
     engine = Engine("fill", args.model_root, synthetic=args.synthetic_weights, tiny=args.tiny, device=torch.device("cuda", local),
-                    text_encoder=args.text_encoder, linear_precision=args.linear_precision)
+                    text_encoder=args.text_encoder, linear_precision=args.linear_precision, step_cache=args.step_cache)
     rng = random.Random(None if args.seed is None else args.seed + rank)
     writer = ImageWriter(args.io_workers)
     done, failed = parse_resume_log(args.log_file) if (args.resume or args.failed_only) else (set(), set())

@@ -18,6 +18,7 @@ only owns the device buffers.  MI355X-first layout decisions:
 from __future__ import annotations
 
 import math
+from typing import NamedTuple, Sequence
 
 import torch
 
@@ -45,6 +46,99 @@ if _LINEAR_PRECISION not in LINEAR_PRECISIONS:
 # the bf16 GEMM) every headline shape measured (MX + quantise) / bf16 between 1.62 and 1.84, so all six stay; the single blocks' 21 504-row
 # weight runs as its 9216- and 12 288-row ranges on the MX route, both listed.
 _MX_STAYS_BF16: frozenset = frozenset({(9216, 3072), (3072, 3072), (12288, 3072), (3072, 12288), (21504, 3072), (3072, 15360)})
+
+
+def parse_step_cache(text: str | None) -> float | None:
+    """a step-cache threshold as the environment / a command line gives it: None, "" and 0 mean off (None); a negative, NaN or unparsable
+    value raises ValueError; ``inf`` is a threshold (every step whose ratio is finite reuses)"""
+    if text is None or str(text).strip() == "":
+        return None
+    try:
+        v = float(text)
+    except (TypeError, ValueError):
+        raise ValueError(f"step cache threshold must be a number >= 0, not {text!r}") from None
+    if math.isnan(v) or v < 0:
+        raise ValueError(f"step cache threshold must be a number >= 0, not {text!r}")
+    return v if v > 0 else None
+
+
+# the first-block step cache (StepCache below; opt-in, no default threshold): $DRAG_STEP_CACHE=<threshold> sets the process default of the
+# pipelines' ``step_cache``, read once; unset, empty or 0 = off
+STEP_CACHE_DEFAULT = parse_step_cache(os.environ.get("DRAG_STEP_CACHE", ""))
+
+
+class StepDecision(NamedTuple):
+    """one forward's entry of ``StepCache.decisions``: the per-image first-block residual ratios against the last computed step (None when
+    there was none to compare with) and whether the step reused that step's cached residual"""
+    ratios: tuple | None
+    reused: bool
+
+
+class StepCache:
+    """First-block cache of the DiT forward (``FluxTransformerHIP.forward(..., cache=...)``): after double block 0 the change of that block's
+    residual since the last COMPUTED step, sum |new - old| / sum |old| per image, is compared with ``threshold``; when every image of the
+    batch is under it, the cached residual of the remaining blocks is added instead of running them.  The comparison is always against the
+    last computed step, so the drift is bounded by the threshold and not by the number of reuses.  A NaN or infinite ratio never reuses.
+
+    ``forced``: for measurement and tests — ``forced[i]`` is the value ``reused`` takes in forward number ``i`` since ``reset()`` whatever
+    the ratios say (a forward with nothing valid to reuse still computes); forwards beyond its length follow the threshold.
+
+    State: three dense bf16 [B, Si, D] buffers — E (scratch: the current first-block residual), F (the first-block residual of the last
+    computed step), R (the residual of that step's remaining blocks, image rows only: the final projection reads nothing else) — the float64
+    ratios and the reduction workspace.  It is invalid after ``reset()``, after a change of (B, Si, D) and after a change of the model's
+    ``linear_precision``.  Reading the ratios back is the one host synchronisation per step."""
+
+    def __init__(self, threshold: float, forced: Sequence[bool] | None = None):
+        self.configure(threshold, forced)
+        self._key = self._precision = None
+        self.E = self.F = self.R = self.ratios = self.workspace = None
+        self.reset()
+
+    def configure(self, threshold: float, forced: Sequence[bool] | None = None) -> None:
+        threshold = float(threshold)
+        if math.isnan(threshold) or threshold < 0:
+            raise ValueError(f"StepCache threshold must be >= 0, not {threshold!r}")
+        self.threshold = threshold
+        self.forced = None if forced is None else [bool(v) for v in forced]
+
+    def reset(self) -> None:
+        self.valid = False
+        self.decisions: list[StepDecision] = []
+
+    def _prepare(self, B: int, Si: int, D: int, precision: str, device) -> None:
+        key = (B, Si, D, str(device))
+        if self._key != key:
+            bf = dict(dtype=torch.bfloat16, device=device)
+            self.E, self.F, self.R = (torch.empty((B, Si, D), **bf) for _ in range(3))
+            self.ratios = torch.empty(B, dtype=torch.float64, device=device)
+            self.workspace = torch.empty(ops.stepcache_workspace_bytes(B, Si, D), dtype=torch.uint8, device=device)
+            self._key, self.valid = key, False
+        if self._precision != precision:
+            self._precision, self.valid = precision, False
+
+    def _decide(self) -> bool:
+        """after ``stepcache_delta``: read the ratios back, record the decision, return ``reused``"""
+        ratios = tuple(self.ratios.cpu().tolist()) if self.valid else None
+        n = len(self.decisions)
+        if self.forced is not None and n < len(self.forced):
+            want = self.forced[n]
+        else:
+            want = ratios is not None and all(r < self.threshold for r in ratios)      # NaN and +inf compare False
+        reused = bool(self.valid and want)
+        self.decisions.append(StepDecision(ratios, reused))
+        return reused
+
+
+def pipeline_step_cache(cache: StepCache | None, threshold: float | None, forced: Sequence[bool] | None = None) -> StepCache | None:
+    """the cache one pipeline call runs with: None when the mode is off (``threshold`` None or 0); else the pipeline's one StepCache (its
+    buffers are kept from call to call), brought to ``threshold`` / ``forced`` and RESET, so that no state leaks between samples"""
+    if threshold is None or float(threshold) == 0:
+        return None
+    if cache is None:
+        return StepCache(threshold, forced)
+    cache.configure(threshold, forced)
+    cache.reset()
+    return cache
 
 
 def rope_tables(ids: torch.Tensor, axes_dims=(16, 56, 56), theta: float = 10000.0):
@@ -263,10 +357,16 @@ class FluxTransformerHIP:
         h = ops.gemm(pooled, w[pre + "text_embedder.linear_1.weight"], bias=w[pre + "text_embedder.linear_1.bias"], act=ops.ACT_SILU)
         return ops.gemm(h, w[pre + "text_embedder.linear_2.weight"], bias=w[pre + "text_embedder.linear_2.bias"], resid=emb)
 
-    def forward(self, hidden, enc, pooled, timestep, img_ids, txt_ids, guidance=None, taps: dict | None = None):
+    def forward(self, hidden, enc, pooled, timestep, img_ids, txt_ids, guidance=None, taps: dict | None = None,
+                cache: StepCache | None = None):
         """hidden bf16 [B, S_img, in]; enc bf16 [B, S_txt, J]; pooled bf16 [B, P]; timestep / guidance
-        fp32 [B] host or device; returns bf16 [B, S_img, out] (a view of an internal workspace)."""
+        fp32 [B] host or device; returns bf16 [B, S_img, out] (a view of an internal workspace).
+        ``cache``: a :class:`StepCache` (opt-in; None is the plain forward, the same launches in the same order): the first double block
+        runs, then the step either reuses the cached residual of the remaining blocks or computes them and refreshes the cache."""
         cfg = self.cfg
+        if cache is not None and (cfg.num_layers < 1 or cfg.num_layers + cfg.num_single_layers < 2):
+            raise ValueError("a step cache needs a double block and at least one further block")
+        reused = False
         D, H = cfg.dim, cfg.num_attention_heads
         F = cfg.mlp_ratio * D
         B, Si, _ = hidden.shape
@@ -312,6 +412,9 @@ class FluxTransformerHIP:
 
         for i, blk in enumerate(self.double):
             mo, cmo = self.mod_off[(i, "norm1")], self.mod_off[(i, "norm1_context")]
+            if cache is not None and i == 0:      # step cache, hook 1: the image rows as block 0 receives them
+                cache._prepare(B, Si, D, self._linear_precision, self.device)
+                cache.E.copy_(x[:, St:])
             # chunk order: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
             ops.layernorm(x_img, nrm_img, Mi, D, scale=modv[mo + D:], shift=modv[mo:], ldx=D, rows_per_batch=Si,
                           x_batch_stride=S * D, ld_mod=LM)
@@ -347,12 +450,27 @@ class FluxTransformerHIP:
                                    c_batch_stride=S * D, ldc=D, gate=modv[cmo + 5 * D:], resid=x, ldg=LM))
             if taps is not None:
                 taps[f"double.{i}"] = x.clone()
+            if cache is not None and i == 0:
+                # step cache, hook 2: E <- block 0's residual of the image rows, its ratio against the last computed step's (F), the decision
+                ops.stepcache_delta(x_img, cache.E, cache.F if cache.valid else None, cache.ratios, cache.workspace, B, Si, D, S * D)
+                if taps is not None:
+                    taps["cache.delta"] = cache.E.clone()
+                reused = cache._decide()
+                if reused:      # add that step's residual of the remaining blocks and go to the final LayerNorm; F and R stay
+                    ops.stepcache_apply(x_img, cache.R, B, Si, D, S * D, +1)
+                    if taps is not None:
+                        taps["cache.x_img"] = x[:, St:].clone()
+                    break
+                # hook 3, computed step: this residual becomes F; R <- the image rows now, turned into the residual after the last block
+                cache.E, cache.F = cache.F, cache.E
+                cache.valid = False
+                cache.R.copy_(x[:, St:])
 
         cat_mlp = catb.view(-1)[D:]
         fused_qkv_mlp = (3 * D) % 256 == 0 and (_FUSED_QKV_MLP if _FUSED_QKV_MLP is not None else
                                                 ops.gemm_cost(M, 3 * D + F, D) * 10 <= (ops.gemm_cost(M, 3 * D, D) + ops.gemm_cost(M, F, D)) * 9)
         mx_qkv, mx_mlp, mx_out = self._mx_moves(3 * D, D), self._mx_moves(F, D), self._mx_moves(D, D + F)
-        for i, blk in enumerate(self.single):
+        for i, blk in enumerate(() if reused else self.single):
             mo = self.mod_off[("s", i)]      # shift, scale, gate
             ops.layernorm(x, nrm, M, D, scale=modv[mo + D:], shift=modv[mo:], ldx=D, ld_mod=LM, rows_per_batch=S,
                           x_batch_stride=S * D)
@@ -388,6 +506,9 @@ class FluxTransformerHIP:
             if taps is not None:
                 taps[f"single.{i}"] = x.clone()
 
+        if cache is not None and not reused:
+            ops.stepcache_apply(x_img, cache.R, B, Si, D, S * D, -1)      # capture: R <- x_img - (x_img after block 0)
+            cache.valid = True
         mo = self.mod_off["out"]             # AdaLayerNormContinuous: scale, shift
         ops.layernorm(x_img, nrm_img, Mi, D, scale=modv[mo:], shift=modv[mo + D:], ldx=D, rows_per_batch=Si,
                       x_batch_stride=S * D, ld_mod=LM)
@@ -398,7 +519,7 @@ class FluxTransformerHIP:
     # ------------------------------------------------------------------ hipGraph replay
     MAX_GRAPHS = 3          # captured forwards kept alive (each owns a workspace: ~1 GB per image at 1024^2)
 
-    def forward_graphed(self, hidden, enc, pooled, timestep, img_ids, txt_ids, guidance=None):
+    def forward_graphed(self, hidden, enc, pooled, timestep, img_ids, txt_ids, guidance=None, cache: StepCache | None = None):
         """Same result as ``forward`` (bit-identical: same kernels, same order), but the ~800 launches of one forward
         are captured ONCE into a hipGraph and replayed; only the timestep / guidance values change between replays and
         travel through device buffers updated before the launch.  The GPU was never launch-bound (host enqueue 4.8 ms
@@ -407,7 +528,9 @@ class FluxTransformerHIP:
         RoPE tables and time buffers (they must not be freed or reused while the graph lives), is keyed on the input
         addresses, the shapes AND the RoPE table identity (the same token count can be a different h x w), and the
         cache is a small LRU (image sizes vary from sample to sample in stage 3).  The Linear precision is part of the key: the two modes
-        are different launch sequences."""
+        are different launch sequences.  A step cache cannot be replayed: its decision needs the host between two pieces of the forward."""
+        if cache is not None:
+            raise ValueError("forward_graphed takes no step cache (the decision needs the host): call forward(..., cache=...)")
         t = torch.as_tensor(timestep, dtype=torch.float32).cpu().reshape(-1)
         g = None if guidance is None else torch.as_tensor(guidance, dtype=torch.float32).cpu().reshape(-1)
         rope_key = self._ids_key(txt_ids, img_ids)

@@ -502,6 +502,58 @@ def layernorm(x: torch.Tensor, y: torch.Tensor, M: int, D: int, *, scale=None, s
     return y
 
 
+def _stepcache_room(x: torch.Tensor, dense: dict, B: int, rows_per_batch: int, cols: int, x_batch_stride: int, what: str) -> None:
+    """the last element each operand's addressing reaches must lie inside its storage: a wrong stride is an error here, not a memory fault
+    in the kernel (shapes the library refuses are the library's to report)"""
+    if B <= 0 or rows_per_batch <= 0 or cols <= 0 or x_batch_stride < rows_per_batch * cols:
+        return
+    n = rows_per_batch * cols
+    if (B - 1) * x_batch_stride + n > _room(x):
+        raise ValueError(f"{what}.x: {B} images of {n} elements, batch stride {x_batch_stride}, do not fit ({_room(x)} elements from its start)")
+    for name, t in dense.items():
+        if t is not None and (not t.is_contiguous() or t.numel() < B * n):
+            raise ValueError(f"{what}.{name}: expected a contiguous tensor of at least {B * n} elements")
+
+
+def stepcache_workspace_bytes(B: int, rows_per_batch: int, cols: int) -> int:
+    """bytes of the partial-sum workspace ``stepcache_delta`` needs for this shape (``drag_stepcache_workspace_bytes``); launches nothing"""
+    return int(_lib.load().drag_stepcache_workspace_bytes(B, rows_per_batch, cols))
+
+
+def stepcache_delta(x: torch.Tensor, e: torch.Tensor, f: torch.Tensor | None, ratios: torch.Tensor | None, workspace: torch.Tensor | None,
+                    B: int, rows_per_batch: int, cols: int, x_batch_stride: int) -> None:
+    """in place ``e <- bf16(f32(x) - f32(e))``; with ``f`` also ``ratios[b] = sum |e - f| / sum |f|`` per image in float64
+    (``drag_stepcache_delta_bf16``).  ``x`` addresses image rows as ``layernorm`` does (``rows_per_batch`` rows of ``cols`` elements from
+    ``x`` on, ``x_batch_stride`` between images); ``e`` / ``f`` are dense [B, rows_per_batch, cols]; ``ratios`` float64 [B]; ``workspace``
+    uint8, ``stepcache_workspace_bytes`` long.  With ``f`` None no ratio is written."""
+    lib = _lib.load()
+    _need(x, torch.bfloat16, "stepcache_delta.x")
+    _need(e, torch.bfloat16, "stepcache_delta.e")
+    if f is not None:
+        _need(f, torch.bfloat16, "stepcache_delta.f")
+        if ratios is None or workspace is None:
+            raise ValueError("stepcache_delta: f given, so ratios and workspace are required")
+        _need(ratios, torch.float64, "stepcache_delta.ratios")
+        _need(workspace, torch.uint8, "stepcache_delta.workspace")
+        if ratios.numel() < B or not ratios.is_contiguous():
+            raise ValueError(f"stepcache_delta.ratios: expected a contiguous float64 tensor of at least {B} elements")
+        if workspace.numel() < stepcache_workspace_bytes(B, rows_per_batch, cols):
+            raise ValueError(f"stepcache_delta.workspace: {workspace.numel()} bytes, {stepcache_workspace_bytes(B, rows_per_batch, cols)} needed")
+    _stepcache_room(x, dict(e=e, f=f), B, rows_per_batch, cols, x_batch_stride, "stepcache_delta")
+    check(lib.drag_stepcache_delta_bf16(_p(x), _p(e), _p(f), _p(ratios) if f is not None else None, _p(workspace) if f is not None else None,
+                                        B, rows_per_batch, cols, x_batch_stride, _stream()), "drag_stepcache_delta_bf16")
+
+
+def stepcache_apply(x: torch.Tensor, r: torch.Tensor, B: int, rows_per_batch: int, cols: int, x_batch_stride: int, sign: int) -> None:
+    """``sign`` = +1: ``x <- bf16(f32(x) + f32(r))``; -1, the capture form: ``r <- bf16(f32(x) - f32(r))`` (``drag_stepcache_apply_bf16``).
+    ``x`` addressed as in ``stepcache_delta``, ``r`` dense [B, rows_per_batch, cols]."""
+    lib = _lib.load()
+    _need(x, torch.bfloat16, "stepcache_apply.x")
+    _need(r, torch.bfloat16, "stepcache_apply.r")
+    _stepcache_room(x, dict(r=r), B, rows_per_batch, cols, x_batch_stride, "stepcache_apply")
+    check(lib.drag_stepcache_apply_bf16(_p(x), _p(r), B, rows_per_batch, cols, x_batch_stride, sign, _stream()), "drag_stepcache_apply_bf16")
+
+
 def act(x: torch.Tensor, kind: int, out: torch.Tensor | None = None) -> torch.Tensor:
     lib = _lib.load()
     _need(x, torch.bfloat16, "x")

@@ -282,6 +282,25 @@ int drag_layernorm_modulate_bf16(const void* x, void* y, const void* scale, cons
                                  int32_t ldx, int32_t rows_per_batch, int64_t x_batch_stride,
                                  int32_t ldy, int32_t ld_mod, float eps, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * First-block step cache of the Flux DiT (opt-in; the default forward calls neither of these).  Both address the image rows of the joint
+ * activation buffer as drag_layernorm_modulate_bf16 does: batch b's rows_per_batch rows of cols bf16 elements (row stride cols) start at
+ * x + b * x_batch_stride; e, f and r are dense [B, rows_per_batch, cols].  Both validate before the launch (null pointers, cols % 8,
+ * x_batch_stride < rows_per_batch * cols, 16-byte alignment): a refused call returns -1 and launches nothing.
+ *
+ * drag_stepcache_delta_bf16 — in place e <- bf16(f32(x) - f32(e)).  With f != NULL also, per image b over the STORED (rounded) e,
+ *   ratios[b] = sum |e - f| / sum |f|   as float64: +inf when the denominator is 0, NaN when any term is.  Every term is formed and summed
+ * in float64 (bf16 -> float64 is exact: only the order of summation separates the result from a float64 reference); workgroup partials go
+ * to `workspace` (drag_stepcache_workspace_bytes bytes, 8-byte aligned) and a second launch combines them in a fixed order, so the same
+ * input gives the same 64 bits on every run.  With f == NULL nothing is written to ratios (it and workspace may be NULL). */
+int64_t drag_stepcache_workspace_bytes(int32_t B, int32_t rows_per_batch, int32_t cols);
+int drag_stepcache_delta_bf16(const void* x, void* e, const void* f, double* ratios, void* workspace, int32_t B, int32_t rows_per_batch,
+                              int32_t cols, int64_t x_batch_stride, void* stream);
+/* drag_stepcache_apply_bf16 — sign = +1: x <- bf16(f32(x) + f32(r)) (a reused step adds the cached residual);
+ * sign = -1, the capture form: r <- bf16(f32(x) - f32(r)), r holding a saved copy of the earlier x. */
+int drag_stepcache_apply_bf16(void* x, void* r, int32_t B, int32_t rows_per_batch, int32_t cols, int64_t x_batch_stride, int32_t sign,
+                              void* stream);
+
 /* elementwise helpers (bf16) */
 int drag_act_bf16(const void* x, void* y, int64_t n, int32_t act, void* stream);
 /* sinusoidal embedding as diffusers get_timestep_embedding(t, dim, flip_sin_to_cos=True,

@@ -264,7 +264,10 @@ def _hip_pipes(args, kind, encoders):
     prior = compat.FluxPriorReduxPipeline.from_pretrained(os.path.join(args.model_root, "FLUX.1-Redux-dev"), text_encoder=te, text_encoder_2=te2,
                                                           tokenizer=tok, tokenizer_2=tok2).to("cuda")
     cls = compat.FluxFillPipeline if kind == "fill" else compat.FluxPipeline
-    return prior, cls.from_pretrained(flux).to("cuda")
+    pipe = cls.from_pretrained(flux).to("cuda")
+    if getattr(args, "step_cache", None):       # --step-cache: the HIP side runs with the first-block step cache (flux.StepCache)
+        pipe.pipe.step_cache = args.step_cache
+    return prior, pipe
 
 
 def _prior_delta(ref_out, hip_out) -> dict:
@@ -351,6 +354,8 @@ def main(argv=None) -> int:
     ap.add_argument("--strength", type=float, default=0.6)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default="accept_report.json")
+    ap.add_argument("--step-cache", type=float, default=None, metavar="THRESHOLD",
+                    help="run the HIP stage-2 / stage-3 pipelines with the first-block step cache at this threshold (default: off)")
     args = ap.parse_args(argv)
     sections = [s for s in args.sections.split(",") if s]
     bad = [s for s in sections if s not in SECTIONS]
@@ -359,6 +364,8 @@ def main(argv=None) -> int:
     info = probe(args.model_root, sections)
     report = {"sections_requested": sections, "tolerances": {"pixels_rel_full_scale": PIXEL_REL_TOL, "latents_rel_max": LATENT_REL_TOL,
                                                              "topk": "indices bit-exact"}, "missing": info["missing"]}
+    if args.step_cache:
+        report["step_cache"] = args.step_cache
     if any(s in sections for s in ("stage2", "stage3")) and not args.target:
         report["missing"].append("--target <inpainted k-shot image>")
     if report["missing"]:
