@@ -49,7 +49,12 @@ def build_parser():
     p.add_argument("--step_cache", type=parse_step_cache, default=None, metavar="THRESHOLD",
                    help="first-block step cache of the denoise loop (opt-in, lower fidelity): a step whose first-block residual moved by less "
                         "than THRESHOLD (relative L1, every image of the batch) since the last computed step reuses that step's remaining "
-                        "blocks; batch neighbours then influence a result (--ref_batch 1 restores independence); default: $DRAG_STEP_CACHE, else off")
+                        "blocks; batch neighbours then influence a result (--step_cache_scope image or --ref_batch 1 restores independence); "
+                        "default: $DRAG_STEP_CACHE, else off")
+    p.add_argument("--step_cache_scope", choices=["batch", "image"], default=None,
+                   help="who decides a reuse when --step_cache is on: batch = every image of the batch must be under the threshold; image = "
+                        "every image decides for itself and the remaining blocks run on the others only, so a result does not depend on its "
+                        "batch neighbours; default: $DRAG_STEP_CACHE_SCOPE, else batch")
     p.add_argument("--text_encoder", choices=["transformers", "hip"], default="transformers",
                    help="what encodes a prompt without a prompt_cache file: the transformers T5 / CLIP modules (eager torch) or the HIP "
                         "encoders (domain_rag_amd.textenc); tokenizers are host Python either way")
@@ -68,9 +73,12 @@ DATASET_GROUPS = {"dataset1": ["ArTaxOr", "clipart1k"], "dataset2": ["DIOR", "FI
                   "dataset4": ["NWPU_VHR_10", "Camouflage"]}
 
 
-def params_txt_step_cache(step_cache) -> str:
-    """the line params.txt gains when the step cache is on; nothing when it is off (the file is then byte-identical to the reference's)"""
-    return f"步骤缓存阈值: {step_cache}\n" if step_cache else ""
+def params_txt_step_cache(step_cache, scope: str = "batch") -> str:
+    """the line params.txt gains when the step cache is on, and one more when its scope is "image"; nothing when it is off (the file is then
+    byte-identical to the reference's)"""
+    if not step_cache:
+        return ""
+    return f"步骤缓存阈值: {step_cache}\n" + (f"步骤缓存范围: {scope}\n" if scope == "image" else "")
 
 
 def generate_ranked(engine: Engine, target_path, items, sdir, args, database):
@@ -130,7 +138,7 @@ def generate_ranked(engine: Engine, target_path, items, sdir, args, database):
                         f.write(f"数据库类型: {database}\n参考图像权重: {COCO_IMAGE_SCALE}\n目标图像权重: {TARGET_IMAGE_SCALE}\n"
                                 f"参考文本权重: {COCO_TEXT_SCALE}\n目标文本权重: {TARGET_TEXT_SCALE}\n提示词: {PROMPT}\n指导比例: {GUIDANCE}\n"
                                 f"推理步数: {args.num_inference_steps}\n生成图像尺寸: {w}x{h}\n原始图像尺寸: {tgt_img.size[0]}x{tgt_img.size[1]}\n"
-                                + params_txt_step_cache(getattr(engine.pipe, "step_cache", None)))
+                                + params_txt_step_cache(getattr(engine.pipe, "step_cache", None), getattr(engine.pipe, "step_cache_scope", "batch")))
                 rs = f"rank{rank}" if rank is not None else ""
                 ss = f"_sim{similarity:.4f}" if similarity is not None else ""
                 with open(os.path.join(sdir, f"ref_info{rs}{ss}.txt"), "w") as f:
@@ -288,7 +296,8 @@ def main(argv=None):
     from ..io_pool import ImageWriter
     args.writer = ImageWriter(args.io_workers)
     engine = Engine("dev", args.model_root, synthetic=args.synthetic_weights, tiny=args.tiny, device=torch.device("cuda", local),
-                    text_encoder=args.text_encoder, linear_precision=args.linear_precision, step_cache=args.step_cache)
+                    text_encoder=args.text_encoder, linear_precision=args.linear_precision, step_cache=args.step_cache,
+                    step_cache_scope=args.step_cache_scope)
     datasets = [args.dataset] if args.dataset else (DATASET_GROUPS[args.dataset_group] if args.dataset_group else list(results))
     tot_ok = tot_bad = 0
     for ds in datasets:

@@ -71,7 +71,12 @@ def build_parser():
     p.add_argument("--step_cache", type=parse_step_cache, default=None, metavar="THRESHOLD",
                    help="first-block step cache of the denoise loop (opt-in, lower fidelity): a step whose first-block residual moved by less "
                         "than THRESHOLD (relative L1, every image of the batch) since the last computed step reuses that step's remaining "
-                        "blocks; batch neighbours then influence a result (--bg_batch 1 restores independence); default: $DRAG_STEP_CACHE, else off")
+                        "blocks; batch neighbours then influence a result (--step_cache_scope image or --bg_batch 1 restores independence); "
+                        "default: $DRAG_STEP_CACHE, else off")
+    p.add_argument("--step_cache_scope", choices=["batch", "image"], default=None,
+                   help="who decides a reuse when --step_cache is on: batch = every image of the batch must be under the threshold; image = "
+                        "every image decides for itself and the remaining blocks run on the others only, so a result does not depend on its "
+                        "batch neighbours; default: $DRAG_STEP_CACHE_SCOPE, else batch")
     p.add_argument("--text_encoder", choices=["transformers", "hip"], default="transformers",
                    help="what encodes a prompt without a prompt_cache file: the transformers T5 / CLIP modules (eager torch) or the HIP "
                         "encoders (domain_rag_amd.textenc); tokenizers are host Python either way")
@@ -87,9 +92,12 @@ def build_parser():
     return p
 
 
-def step_cache_params(step_cache) -> dict:
-    """what a result's parameter JSON gains when the step cache is on; nothing when it is off (the file is then byte-identical)"""
-    return {"step_cache": step_cache} if step_cache else {}
+def step_cache_params(step_cache, scope: str = "batch") -> dict:
+    """what a result's parameter JSON gains when the step cache is on (and ``step_cache_scope`` when that is "image"); nothing when it is off
+    (the file is then byte-identical)"""
+    if not step_cache:
+        return {}
+    return {"step_cache": step_cache, **({"step_cache_scope": scope} if scope == "image" else {})}
 
 
 def dataset_result_dirs(result_dir, dataset, shot):
@@ -273,7 +281,7 @@ def process_sample(engine: Engine, args, dataset, sample_id, sample_dir, shot, p
                           "min_dimension_used": min_dim, "up_scale_factor": up, "down_scale_factor": down, "was_upscaled": wu,
                           "was_downscaled": wd, "bbox_coords_list": bboxes, "processed_bbox_coords_list": pb,
                           "image_id": info["id"] if info.get("id") is not None else "unknown", "num_bbox": len(bboxes)}
-                params.update(step_cache_params(getattr(engine.pipe, "step_cache", None)))
+                params.update(step_cache_params(getattr(engine.pipe, "step_cache", None), getattr(engine.pipe, "step_cache_scope", "batch")))
                 params_path = os.path.join(out_dir, f"{prefix}_params{suffix}.json")
                 with open(params_path, "w") as f:
                     json.dump(params, f, indent=2)
@@ -318,7 +326,8 @@ def run_rank(args, datasets, process_id, rank, world, gpu_process_id=None):
     local = int(os.environ.get("LOCAL_RANK", str(rank))) % max(torch.cuda.device_count(), 1)   # (more ranks than GPUs: share them)
     torch.cuda.set_device(local)
     engine = Engine("fill", args.model_root, synthetic=args.synthetic_weights, tiny=args.tiny, device=torch.device("cuda", local),
-                    text_encoder=args.text_encoder, linear_precision=args.linear_precision, step_cache=args.step_cache)
+                    text_encoder=args.text_encoder, linear_precision=args.linear_precision, step_cache=args.step_cache,
+                    step_cache_scope=args.step_cache_scope)
     rng = random.Random(None if args.seed is None else args.seed + rank)
     writer = ImageWriter(args.io_workers)
     done, failed = parse_resume_log(args.log_file) if (args.resume or args.failed_only) else (set(), set())

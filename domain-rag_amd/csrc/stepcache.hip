@@ -1,6 +1,6 @@
-// stepcache.hip — the two kernels of the first-block step cache of the Flux DiT (flux.StepCache; opt-in, the default forward calls neither).
+// stepcache.hip — the kernels of the first-block step cache of the Flux DiT (flux.StepCache; opt-in, the default forward calls none of them).
 //
-// Both address image rows as drag_layernorm_modulate_bf16 does: `rows_per_batch` rows of `cols` bf16 elements, row stride `cols`, batch
+// All address image rows as drag_layernorm_modulate_bf16 does: `rows_per_batch` rows of `cols` bf16 elements, row stride `cols`, batch
 // stride `x_batch_stride` — an image's rows are one contiguous run of rows_per_batch * cols elements inside the joint [B, S, D] buffer,
 // behind its text rows.  The dense operands (e, f, r) are [B, rows_per_batch, cols].
 //
@@ -8,6 +8,10 @@
 // grid-strided.  The residual ratio is summed in float64 from the first term on (bf16 -> float64 is exact, so only the order of summation
 // separates the result from a float64 reference), per workgroup into `workspace`, then combined by a second launch in a fixed order: no
 // floating-point atomics, the same input gives the same 64 bits on every run.
+//
+// The *_images / swap forms (StepCache scope "image": every image decides for itself) work on a LIST of images or of image pairs.  The list
+// is a host array: the entry point validates it (range, order, disjointness) and copies it into the kernel's argument struct, so no index
+// a kernel reads can lie outside [0, B).  blockIdx.y walks the list; the element loop is the whole-batch kernels'.
 #include "drag_common.h"
 
 #include <math.h>
@@ -108,13 +112,9 @@ __global__ __launch_bounds__(64) void stepcache_ratio_kernel(const double* __res
   }
 }
 
-// ADD: x <- bf16(f32(x) + f32(r)) (x strided, r dense); else the capture form r <- bf16(f32(x) - f32(r))
+// one image: ADD: x <- bf16(f32(x) + f32(r)); else the capture form r <- bf16(f32(x) - f32(r))
 template <bool ADD>
-__global__ __launch_bounds__(SC_THREADS) void stepcache_apply_kernel(bf16_t* __restrict__ x, bf16_t* __restrict__ r, long long n8,
-                                                                     long long x_bs) {
-  const int b = blockIdx.y;
-  bf16_t* xb = x + (long long)b * x_bs;
-  bf16_t* rb = r + (long long)b * n8 * 8;
+__device__ __forceinline__ void sc_apply_image(bf16_t* __restrict__ xb, bf16_t* __restrict__ rb, long long n8) {
   const long long stride = (long long)gridDim.x * SC_THREADS;
   for (long long i = (long long)blockIdx.x * SC_THREADS + threadIdx.x; i < n8; i += stride) {
     const u32x4_t xr = *(const u32x4_t*)(xb + i * 8);
@@ -130,7 +130,70 @@ __global__ __launch_bounds__(SC_THREADS) void stepcache_apply_kernel(bf16_t* __r
   }
 }
 
+// ADD: x <- bf16(f32(x) + f32(r)) (x strided, r dense); else the capture form r <- bf16(f32(x) - f32(r))
+template <bool ADD>
+__global__ __launch_bounds__(SC_THREADS) void stepcache_apply_kernel(bf16_t* __restrict__ x, bf16_t* __restrict__ r, long long n8,
+                                                                     long long x_bs) {
+  const int b = blockIdx.y;
+  sc_apply_image<ADD>(x + (long long)b * x_bs, r + (long long)b * n8 * 8, n8);
+}
+
+// ---- list forms.  SC_MAX_LIST indices travel in the argument struct (256 bytes), validated on the host
+constexpr int SC_MAX_LIST = 64;
+struct ScList {
+  int32_t v[SC_MAX_LIST];
+};
+
+// the apply kernel on the listed images only; r stays indexed by image
+template <bool ADD>
+__global__ __launch_bounds__(SC_THREADS) void stepcache_apply_images_kernel(bf16_t* __restrict__ x, bf16_t* __restrict__ r, long long n8,
+                                                                            long long x_bs, ScList images) {
+  const int b = images.v[blockIdx.y];
+  sc_apply_image<ADD>(x + (long long)b * x_bs, r + (long long)b * n8 * 8, n8);
+}
+
+// dst[b] <- src[b] for the listed images (dst dense, src with its own batch stride)
+__global__ __launch_bounds__(SC_THREADS) void stepcache_copy_images_kernel(bf16_t* __restrict__ dst, const bf16_t* __restrict__ src,
+                                                                           long long n8, long long src_bs, ScList images) {
+  const int b = images.v[blockIdx.y];
+  bf16_t* db = dst + (long long)b * n8 * 8;
+  const bf16_t* sb = src + (long long)b * src_bs;
+  const long long stride = (long long)gridDim.x * SC_THREADS;
+  for (long long i = (long long)blockIdx.x * SC_THREADS + threadIdx.x; i < n8; i += stride)
+    *(u32x4_t*)(db + i * 8) = *(const u32x4_t*)(sb + i * 8);
+}
+
+// exchange the rows of image pairs.v[2p] with those of image pairs.v[2p + 1], p = blockIdx.y: each lane owns its 16 bytes of both images
+__global__ __launch_bounds__(SC_THREADS) void stepcache_swap_kernel(bf16_t* __restrict__ x, long long n8, long long x_bs, ScList pairs) {
+  bf16_t* a = x + (long long)pairs.v[2 * blockIdx.y] * x_bs;
+  bf16_t* b = x + (long long)pairs.v[2 * blockIdx.y + 1] * x_bs;
+  const long long stride = (long long)gridDim.x * SC_THREADS;
+  for (long long i = (long long)blockIdx.x * SC_THREADS + threadIdx.x; i < n8; i += stride) {
+    const u32x4_t av = *(const u32x4_t*)(a + i * 8);
+    const u32x4_t bv = *(const u32x4_t*)(b + i * 8);
+    *(u32x4_t*)(a + i * 8) = bv;
+    *(u32x4_t*)(b + i * 8) = av;
+  }
+}
+
 inline bool sc_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// a host list of image indices into `out`: at most SC_MAX_LIST entries, each in [0, B); `increasing`: strictly increasing (an image list),
+// else all distinct (the 2 * n_pairs indices of a pair list)
+inline bool sc_take_list(const int32_t* host, int n, int B, bool increasing, ScList* out) {
+  if (!host || n < 0 || n > SC_MAX_LIST) return false;
+  for (int i = 0; i < SC_MAX_LIST; ++i) out->v[i] = 0;
+  for (int i = 0; i < n; ++i) {
+    const int32_t v = host[i];
+    if (v < 0 || v >= B) return false;
+    if (increasing && i > 0 && v <= host[i - 1]) return false;
+    if (!increasing)
+      for (int j = 0; j < i; ++j)
+        if (host[j] == v) return false;
+    out->v[i] = v;
+  }
+  return true;
+}
 
 }  // namespace
 
@@ -181,6 +244,64 @@ extern "C" int drag_stepcache_apply_bf16(void* x, void* r, int32_t B, int32_t ro
   else
     hipLaunchKernelGGL(stepcache_apply_kernel<false>, dim3(gpi, B), dim3(SC_THREADS), 0, (hipStream_t)stream, (bf16_t*)x, (bf16_t*)r, n / 8,
                        (long long)x_batch_stride);
+  DRAG_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- scope "image": the list forms
+
+#define SC_COMMON_CHECKS(name, p0, p1, bs)                                                                                                    \
+  DRAG_CHECK((p0) && (p1), name ": null pointer");                                                                                             \
+  DRAG_CHECK(B > 0 && B <= 65535 && rows_per_batch > 0 && cols > 0 && cols % 8 == 0,                                                           \
+             name ": bad shape (B in 1..65535, rows_per_batch > 0, cols > 0, cols %% 8 == 0)");                                                \
+  const long long n = (long long)rows_per_batch * cols;                                                                                        \
+  DRAG_CHECK((bs) >= n, name ": batch stride < rows_per_batch * cols");                                                                        \
+  DRAG_CHECK((bs) % 8 == 0 && sc_aligned16(p0) && sc_aligned16(p1), name ": pointers must be 16-byte aligned (batch stride %% 8 == 0)")
+
+extern "C" int drag_stepcache_swap_bf16(void* x, int32_t B, int32_t rows_per_batch, int32_t cols, int64_t x_batch_stride,
+                                        const int32_t* pairs, int32_t n_pairs, void* stream) {
+  SC_COMMON_CHECKS("drag_stepcache_swap_bf16", x, x, x_batch_stride);
+  DRAG_CHECK(n_pairs >= 0 && n_pairs <= SC_MAX_LIST / 2, "drag_stepcache_swap_bf16: n_pairs must be in 0..32 (64 indices)");
+  if (n_pairs == 0) return 0;
+  ScList list;
+  DRAG_CHECK(sc_take_list(pairs, 2 * n_pairs, B, false, &list),
+             "drag_stepcache_swap_bf16: pairs must be a host array of distinct image indices in [0, B)");
+  hipLaunchKernelGGL(stepcache_swap_kernel, dim3(sc_blocks_per_image(n_pairs, n / 8), n_pairs), dim3(SC_THREADS), 0, (hipStream_t)stream,
+                     (bf16_t*)x, n / 8, (long long)x_batch_stride, list);
+  DRAG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int drag_stepcache_apply_images_bf16(void* x, void* r, int32_t B, int32_t rows_per_batch, int32_t cols, int64_t x_batch_stride,
+                                                int32_t sign, const int32_t* images, int32_t n_images, void* stream) {
+  SC_COMMON_CHECKS("drag_stepcache_apply_images_bf16", x, r, x_batch_stride);
+  DRAG_CHECK(sign == 1 || sign == -1, "drag_stepcache_apply_images_bf16: sign must be +1 (x += r) or -1 (r = x - r)");
+  DRAG_CHECK(n_images >= 0 && n_images <= SC_MAX_LIST, "drag_stepcache_apply_images_bf16: n_images must be in 0..64");
+  if (n_images == 0) return 0;
+  ScList list;
+  DRAG_CHECK(sc_take_list(images, n_images, B, true, &list),
+             "drag_stepcache_apply_images_bf16: images must be a host array of strictly increasing indices in [0, B)");
+  const dim3 grid(sc_blocks_per_image(n_images, n / 8), n_images);
+  if (sign > 0)
+    hipLaunchKernelGGL(stepcache_apply_images_kernel<true>, grid, dim3(SC_THREADS), 0, (hipStream_t)stream, (bf16_t*)x, (bf16_t*)r, n / 8,
+                       (long long)x_batch_stride, list);
+  else
+    hipLaunchKernelGGL(stepcache_apply_images_kernel<false>, grid, dim3(SC_THREADS), 0, (hipStream_t)stream, (bf16_t*)x, (bf16_t*)r, n / 8,
+                       (long long)x_batch_stride, list);
+  DRAG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int drag_stepcache_copy_images_bf16(void* dst_dense, const void* src, int64_t src_batch_stride, int32_t B, int32_t rows_per_batch,
+                                               int32_t cols, const int32_t* images, int32_t n_images, void* stream) {
+  SC_COMMON_CHECKS("drag_stepcache_copy_images_bf16", dst_dense, src, src_batch_stride);
+  DRAG_CHECK(n_images >= 0 && n_images <= SC_MAX_LIST, "drag_stepcache_copy_images_bf16: n_images must be in 0..64");
+  if (n_images == 0) return 0;
+  ScList list;
+  DRAG_CHECK(sc_take_list(images, n_images, B, true, &list),
+             "drag_stepcache_copy_images_bf16: images must be a host array of strictly increasing indices in [0, B)");
+  hipLaunchKernelGGL(stepcache_copy_images_kernel, dim3(sc_blocks_per_image(n_images, n / 8), n_images), dim3(SC_THREADS), 0,
+                     (hipStream_t)stream, (bf16_t*)dst_dense, (const bf16_t*)src, n / 8, (long long)src_batch_stride, list);
   DRAG_LAUNCH_CHECK();
   return 0;
 }

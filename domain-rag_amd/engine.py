@@ -164,12 +164,14 @@ class FluxTxt2ImgHIP:
     """``FluxPipeline.__call__(prompt_embeds=…, pooled_prompt_embeds=…, guidance_scale, num_inference_steps, height,
     width, generator)`` of stage 2 (batch_generate_flux_kshot.py:467-474)."""
 
-    def __init__(self, transformer: FluxTransformerHIP, vae: "vae_mod.FluxVaeHIP", use_graph: bool = True, step_cache: float | None = None):
+    def __init__(self, transformer: FluxTransformerHIP, vae: "vae_mod.FluxVaeHIP", use_graph: bool = True, step_cache: float | None = None,
+                 step_cache_scope: str | None = None):
         self.tr, self.vae, self.dev, self.use_graph = transformer, vae, transformer.device, use_graph
         # first-block step cache threshold, as FluxFillHIP's: None = $DRAG_STEP_CACHE, else off; 0 = off; on = eager forwards, one cache per call
         self.step_cache = flux_mod.STEP_CACHE_DEFAULT if step_cache is None else step_cache
-        self.step_cache_forced = None
-        self.last_step_decisions = None
+        self.step_cache_scope = flux_mod.STEP_CACHE_SCOPE_DEFAULT if step_cache_scope is None else flux_mod.parse_step_cache_scope(step_cache_scope)
+        self.step_cache_forced = self.step_cache_forced_images = None
+        self.last_step_decisions = self.last_step_reused_images = None
         self._cache = None
 
     def __call__(self, prompt_embeds, pooled, *, height: int, width: int, guidance_scale: float, num_inference_steps: int,
@@ -188,7 +190,8 @@ class FluxTxt2ImgHIP:
         sigmas, timesteps = flow_sigmas(num_inference_steps, h * w)
         img_ids, txt_ids = latent_image_ids(h, w), torch.zeros(prompt_embeds.shape[1], 3)
         guidance = torch.full((B,), float(guidance_scale)) if self.tr.cfg.guidance_embeds else None
-        cache = self._cache = flux_mod.pipeline_step_cache(self._cache, self.step_cache, self.step_cache_forced)
+        cache = self._cache = flux_mod.pipeline_step_cache(self._cache, self.step_cache, self.step_cache_forced, self.step_cache_scope,
+                                                                 self.step_cache_forced_images)
         for i in range(num_inference_steps):
             t = torch.full((B,), model_timestep(timesteps[i]))
             if cache is not None:
@@ -200,6 +203,7 @@ class FluxTxt2ImgHIP:
             if on_step is not None:
                 on_step(i, lat.clone())
         self.last_step_decisions = None if cache is None else list(cache.decisions)
+        self.last_step_reused_images = None if cache is None else list(cache.reused_images)
         return self.vae.decode_tokens(lat, B, h, w, ld=64).clone()      # the decoder's buffer is reused by the next call
 
 
@@ -207,12 +211,14 @@ class Engine:
     """Everything stage 2 / stage 3 need, loaded once."""
 
     def __init__(self, kind: str, model_root: str = "./model", synthetic: bool = False, tiny: bool = False, device="cuda",
-                 seed: int = 0, text_encoder: str = "transformers", linear_precision: str | None = None, step_cache: float | None = None):
+                 seed: int = 0, text_encoder: str = "transformers", linear_precision: str | None = None, step_cache: float | None = None,
+                 step_cache_scope: str | None = None):
         """``text_encoder``: what encodes a prompt-cache miss — "transformers" (the reference's modules, eager torch) or "hip"
         (:mod:`.textenc`; with ``synthetic``: seeded encoders and stand-in tokenizers, results kept in memory).
         ``linear_precision``: the DiT blocks' Linears, "bf16" or "mxfp8" (None: $DRAG_LINEAR_PRECISION, else bf16; :mod:`.flux`).
         ``step_cache``: threshold of the first-block step cache of the denoise loop (:class:`.flux.StepCache`; None: $DRAG_STEP_CACHE, else
-        off; 0: off) — the pipeline's ``step_cache`` attribute"""
+        off; 0: off) — the pipeline's ``step_cache`` attribute; ``step_cache_scope``: who decides a reuse, "batch" (the whole batch) or
+        "image" (every image for itself; None: $DRAG_STEP_CACHE_SCOPE, else "batch") — the pipeline's ``step_cache_scope``"""
         assert kind in ("dev", "fill")
         if text_encoder not in ("transformers", "hip"):
             raise ValueError(f"text_encoder must be 'transformers' or 'hip', not {text_encoder!r}")
@@ -243,7 +249,7 @@ class Engine:
         del tp, vp
         self.cfg, self.vit_cfg = cfg, vitcfg
         self.prior = redux_mod.ReduxPriorHIP(vitcfg, vitp, rp, dev)
-        self.pipe = FluxFillHIP(tr, vae, step_cache=step_cache) if kind == "fill" else FluxTxt2ImgHIP(tr, vae, step_cache=step_cache)
+        self.pipe = (FluxFillHIP if kind == "fill" else FluxTxt2ImgHIP)(tr, vae, step_cache=step_cache, step_cache_scope=step_cache_scope)
         Lt, J, P = TINY["t5_tokens"] if tiny else redux_mod.T5_TOKENS, cfg.joint_attention_dim, cfg.pooled_projection_dim
         if text_encoder == "hip" and synthetic:
             self.text = TextCache(model_root, False, Lt, J, P, dev, persist=False,

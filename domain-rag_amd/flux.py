@@ -67,43 +67,101 @@ def parse_step_cache(text: str | None) -> float | None:
 STEP_CACHE_DEFAULT = parse_step_cache(os.environ.get("DRAG_STEP_CACHE", ""))
 
 
+STEP_CACHE_SCOPES = ("batch", "image")
+
+
+def parse_step_cache_scope(text: str | None) -> str:
+    """a step-cache scope as the environment / a command line gives it: None and "" mean "batch"; anything but "batch" / "image" raises"""
+    if text is None or str(text).strip() == "":
+        return "batch"
+    scope = str(text).strip()
+    if scope not in STEP_CACHE_SCOPES:
+        raise ValueError(f"step cache scope must be one of {STEP_CACHE_SCOPES}, not {text!r}")
+    return scope
+
+
+# who decides a reuse: "batch" (the batch as a whole: every image under the threshold) or "image" (every image for itself; the remaining
+# blocks run on the computing images only); $DRAG_STEP_CACHE_SCOPE sets the process default of the pipelines' ``step_cache_scope``, read once
+STEP_CACHE_SCOPE_DEFAULT = parse_step_cache_scope(os.environ.get("DRAG_STEP_CACHE_SCOPE", ""))
+
+
 class StepDecision(NamedTuple):
     """one forward's entry of ``StepCache.decisions``: the per-image first-block residual ratios against the last computed step (None when
-    there was none to compare with) and whether the step reused that step's cached residual"""
+    there was none to compare with) and whether the step reused that step's cached residual (scope "image": whether EVERY image did;
+    ``StepCache.reused_images`` has the per-image answer)"""
     ratios: tuple | None
     reused: bool
 
 
+def compact_pairs(reused: Sequence[bool]) -> tuple:
+    """``(k, pairs)`` that bring the computing images of a batch to its front: ``k`` is the number of computing (not reused) images, and
+    ``pairs`` exchange each reusing image that sits in a slot < k with a computing image that sits in a slot >= k, both taken in increasing
+    order (there are equally many of each).  After the swaps slots 0 ... k-1 hold exactly the computing images; the same swaps again
+    restore the order; a batch that is already compact gives no pairs."""
+    reused = [bool(r) for r in reused]
+    k = reused.count(False)
+    front = [i for i in range(k) if reused[i]]
+    back = [i for i in range(k, len(reused)) if not reused[i]]
+    return k, list(zip(front, back))
+
+
 class StepCache:
     """First-block cache of the DiT forward (``FluxTransformerHIP.forward(..., cache=...)``): after double block 0 the change of that block's
-    residual since the last COMPUTED step, sum |new - old| / sum |old| per image, is compared with ``threshold``; when every image of the
-    batch is under it, the cached residual of the remaining blocks is added instead of running them.  The comparison is always against the
-    last computed step, so the drift is bounded by the threshold and not by the number of reuses.  A NaN or infinite ratio never reuses.
+    residual since the last COMPUTED step, sum |new - old| / sum |old| per image, is compared with ``threshold``.  The comparison is always
+    against the last computed step, so the drift is bounded by the threshold and not by the number of reuses.  A NaN or infinite ratio
+    never reuses.
+
+    ``scope``: "batch" (default) — when every image of the batch is under the threshold, the cached residual of the remaining blocks is
+    added instead of running them; one image over it makes all compute.  "image" — every image decides for itself: the remaining blocks run
+    at batch k on the k computing images, compacted to the front of the workspace, and each reusing image adds its own cached residual, so
+    an image's result does not depend on its batch neighbours.  "last computed step" is then per image.
 
     ``forced``: for measurement and tests — ``forced[i]`` is the value ``reused`` takes in forward number ``i`` since ``reset()`` whatever
     the ratios say (a forward with nothing valid to reuse still computes); forwards beyond its length follow the threshold.
+    ``forced_images`` (scope "image" only): the same per image — ``forced_images[i]`` is a sequence of B bools for forward ``i``.
+
+    ``decisions`` holds one :class:`StepDecision` per forward, ``reused_images`` the per-image tuple of bools next to it (under "batch"
+    all equal).
 
     State: three dense bf16 [B, Si, D] buffers — E (scratch: the current first-block residual), F (the first-block residual of the last
     computed step), R (the residual of that step's remaining blocks, image rows only: the final projection reads nothing else) — the float64
-    ratios and the reduction workspace.  It is invalid after ``reset()``, after a change of (B, Si, D) and after a change of the model's
-    ``linear_precision``.  Reading the ratios back is the one host synchronisation per step."""
+    ratios and the reduction workspace.  Validity is per image (``valid_images``; ``valid``: all of them): every image is invalid after
+    ``reset()``, after a change of (B, Si, D) and after a change of the model's ``linear_precision``.  Reading the ratios back is the one
+    host synchronisation per step."""
 
-    def __init__(self, threshold: float, forced: Sequence[bool] | None = None):
-        self.configure(threshold, forced)
+    def __init__(self, threshold: float, forced: Sequence[bool] | None = None, scope: str = "batch",
+                 forced_images: Sequence[Sequence[bool]] | None = None):
         self._key = self._precision = None
+        self.configure(threshold, forced, scope, forced_images)
         self.E = self.F = self.R = self.ratios = self.workspace = None
         self.reset()
 
-    def configure(self, threshold: float, forced: Sequence[bool] | None = None) -> None:
+    def configure(self, threshold: float, forced: Sequence[bool] | None = None, scope: str = "batch",
+                  forced_images: Sequence[Sequence[bool]] | None = None) -> None:
         threshold = float(threshold)
         if math.isnan(threshold) or threshold < 0:
             raise ValueError(f"StepCache threshold must be >= 0, not {threshold!r}")
+        if scope not in STEP_CACHE_SCOPES:
+            raise ValueError(f"StepCache scope must be one of {STEP_CACHE_SCOPES}, not {scope!r}")
+        if forced_images is not None and scope != "image":
+            raise ValueError('StepCache forced_images needs scope="image" (forced is the whole-batch form)')
         self.threshold = threshold
+        self.scope = scope
         self.forced = None if forced is None else [bool(v) for v in forced]
+        self.forced_images = None if forced_images is None else [tuple(bool(v) for v in m) for m in forced_images]
+
+    @property
+    def valid(self) -> bool:
+        return bool(self.valid_images) and all(self.valid_images)
+
+    @valid.setter
+    def valid(self, value: bool) -> None:
+        self.valid_images = [bool(value)] * (self._key[0] if self._key else 0)
 
     def reset(self) -> None:
         self.valid = False
         self.decisions: list[StepDecision] = []
+        self.reused_images: list[tuple] = []
 
     def _prepare(self, B: int, Si: int, D: int, precision: str, device) -> None:
         key = (B, Si, D, str(device))
@@ -115,28 +173,47 @@ class StepCache:
             self._key, self.valid = key, False
         if self._precision != precision:
             self._precision, self.valid = precision, False
+        if len(self.valid_images) != B:          # reset() before the first forward did not know B
+            self.valid = False
 
-    def _decide(self) -> bool:
-        """after ``stepcache_delta``: read the ratios back, record the decision, return ``reused``"""
-        ratios = tuple(self.ratios.cpu().tolist()) if self.valid else None
-        n = len(self.decisions)
-        if self.forced is not None and n < len(self.forced):
-            want = self.forced[n]
+    def _decide(self) -> tuple:
+        """after ``stepcache_delta``: read the ratios back, record the decision, return the per-image ``reused``"""
+        valid = self.valid_images
+        B, n = len(valid), len(self.decisions)
+        ratios = None
+        if any(valid):
+            ratios = tuple(r if v else None for r, v in zip(self.ratios.cpu().tolist(), valid))
+        if self.scope == "image":
+            if self.forced_images is not None and n < len(self.forced_images):
+                want = self.forced_images[n]
+                if len(want) != B:
+                    raise ValueError(f"StepCache forced_images[{n}] has {len(want)} entries for a batch of {B}")
+            elif self.forced is not None and n < len(self.forced):
+                want = (self.forced[n],) * B
+            else:
+                want = tuple(v and ratios[b] < self.threshold for b, v in enumerate(valid))      # NaN and +inf compare False
+            mask = tuple(bool(v and w) for v, w in zip(valid, want))
         else:
-            want = ratios is not None and all(r < self.threshold for r in ratios)      # NaN and +inf compare False
-        reused = bool(self.valid and want)
-        self.decisions.append(StepDecision(ratios, reused))
-        return reused
+            if self.forced is not None and n < len(self.forced):
+                want = self.forced[n]
+            else:
+                want = self.valid and all(r < self.threshold for r in ratios)      # NaN and +inf compare False
+            mask = (bool(self.valid and want),) * B
+        self.decisions.append(StepDecision(ratios, all(mask)))
+        self.reused_images.append(mask)
+        return mask
 
 
-def pipeline_step_cache(cache: StepCache | None, threshold: float | None, forced: Sequence[bool] | None = None) -> StepCache | None:
+def pipeline_step_cache(cache: StepCache | None, threshold: float | None, forced: Sequence[bool] | None = None, scope: str = "batch",
+                        forced_images: Sequence[Sequence[bool]] | None = None) -> StepCache | None:
     """the cache one pipeline call runs with: None when the mode is off (``threshold`` None or 0); else the pipeline's one StepCache (its
-    buffers are kept from call to call), brought to ``threshold`` / ``forced`` and RESET, so that no state leaks between samples"""
+    buffers are kept from call to call), brought to ``threshold`` / ``forced`` / ``scope`` / ``forced_images`` and RESET, so that no state
+    leaks between samples"""
     if threshold is None or float(threshold) == 0:
         return None
     if cache is None:
-        return StepCache(threshold, forced)
-    cache.configure(threshold, forced)
+        return StepCache(threshold, forced, scope, forced_images)
+    cache.configure(threshold, forced, scope, forced_images)
     cache.reset()
     return cache
 
@@ -357,32 +434,138 @@ class FluxTransformerHIP:
         h = ops.gemm(pooled, w[pre + "text_embedder.linear_1.weight"], bias=w[pre + "text_embedder.linear_1.bias"], act=ops.ACT_SILU)
         return ops.gemm(h, w[pre + "text_embedder.linear_2.weight"], bias=w[pre + "text_embedder.linear_2.bias"], resid=emb)
 
+    # ------------------------------------------------------------------ blocks
+    # Every workspace buffer is batch-leading or flat scratch, so its first ``nb`` slots are the workspace of a batch-``nb`` forward: the
+    # blocks take the batch size they run at (B, or under a step cache of scope "image" the number of computing images).
+    def _double_block(self, ws, i, nb, St, Si, cos, sin, taps):
+        cfg = self.cfg
+        D, H, S, LM = cfg.dim, cfg.num_attention_heads, St + Si, self.mod_total
+        F = cfg.mlp_ratio * D
+        Mi, Mt = nb * Si, nb * St
+        x, nrm, qkv, vt, attn, modv = ws["x"], ws["nrm"], ws["qkv"], ws["vt"], ws["attn"], ws["mod"].view(-1)
+        x_img = x.view(-1)[St * D:]          # joint buffer, image rows of batch 0 onwards
+        nrm_img = nrm.view(-1)[: Mi * D]
+        nrm_txt = nrm.view(-1)[Mi * D: (Mi + Mt) * D]
+        qkv_img = qkv.view(-1)[St * 3 * D:]
+        attn_img = attn.view(-1)[St * D:]
+        hid = ws["cat"].view(-1)              # MLP hidden scratch for double blocks: image rows, then text rows
+        hid_txt = hid[Mi * F:]
+        scale = 1.0 / math.sqrt(cfg.attention_head_dim)
+        blk = self.double[i]
+        mo, cmo = self.mod_off[(i, "norm1")], self.mod_off[(i, "norm1_context")]
+        # chunk order: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
+        ops.layernorm(x_img, nrm_img, Mi, D, scale=modv[mo + D:], shift=modv[mo:], ldx=D, rows_per_batch=Si,
+                      x_batch_stride=S * D, ld_mod=LM)
+        ops.layernorm(x, nrm_txt, Mt, D, scale=modv[cmo + D:], shift=modv[cmo:], ldx=D, rows_per_batch=St,
+                      x_batch_stride=S * D, ld_mod=LM)
+        # the image-stream and text-stream Linears of a pair share N and K: one launch when they are small alone (ops.gemm_pair)
+        self._pair(ws, blk, "wqkv", dict(a=nrm_img, out=qkv_img, bias=blk["bqkv"], M=Mi, lda=D, c_rows_per_batch=Si,
+                                         c_batch_stride=S * 3 * D, ldc=3 * D),
+                   "cwqkv", dict(a=nrm_txt, out=qkv, bias=blk["cbqkv"], M=Mt, lda=D, c_rows_per_batch=St,
+                                 c_batch_stride=S * 3 * D, ldc=3 * D))
+        if _SEPARATE_QPREP:     # A/B switch: the round-1 route (q prepared by the pass, plain attention)
+            ops.qk_norm_rope_vt(qkv, vt, blk["cnq"], blk["cnk"], blk["nq"], blk["nk"], cos, sin, nb, S, H, 3 * D, St)
+            ops.attention(qkv, qkv.view(-1)[D:], vt, attn, nb, S, H, 3 * D, S * 3 * D, D, S * D, scale)
+        else:
+            # k: RMSNorm + RoPE in place, V -> V^T; q: norm_q / norm_added_q + RoPE inside the attention kernel's Q load
+            ops.k_norm_rope_vt(qkv, vt, blk["cnk"], blk["nk"], cos, sin, nb, S, H, 3 * D, St)
+            ops.attention_qprep(qkv, qkv.view(-1)[D:], vt, attn, nb, S, H, 3 * D, S * 3 * D, D, S * D, scale,
+                                blk["cnq"], blk["nq"], cos, sin, St)
+        self._pair(ws, blk, "wo", dict(a=attn_img, out=x_img, bias=blk["bo"], M=Mi, a_rows_per_batch=Si, a_batch_stride=S * D,
+                                       lda=D, c_rows_per_batch=Si, c_batch_stride=S * D, ldc=D, gate=modv[mo + 2 * D:], resid=x_img, ldg=LM),
+                   "cwo", dict(a=attn, out=x, bias=blk["cbo"], M=Mt, a_rows_per_batch=St, a_batch_stride=S * D,
+                               lda=D, c_rows_per_batch=St, c_batch_stride=S * D, ldc=D, gate=modv[cmo + 2 * D:], resid=x, ldg=LM))
+        # MLPs (the two streams are independent: both LayerNorms, both up-projections, both down-projections)
+        ops.layernorm(x_img, nrm_img, Mi, D, scale=modv[mo + 4 * D:], shift=modv[mo + 3 * D:], ldx=D,
+                      rows_per_batch=Si, x_batch_stride=S * D, ld_mod=LM)
+        ops.layernorm(x, nrm_txt, Mt, D, scale=modv[cmo + 4 * D:], shift=modv[cmo + 3 * D:], ldx=D,
+                      rows_per_batch=St, x_batch_stride=S * D, ld_mod=LM)
+        self._pair(ws, blk, "w1", dict(a=nrm_img, out=hid, bias=blk["b1"], act=ops.ACT_GELU_TANH, M=Mi, lda=D, ldc=F),
+                   "cw1", dict(a=nrm_txt, out=hid_txt, bias=blk["cb1"], act=ops.ACT_GELU_TANH, M=Mt, lda=D, ldc=F))
+        self._pair(ws, blk, "w2", dict(a=hid, out=x_img, bias=blk["b2"], M=Mi, lda=F, c_rows_per_batch=Si,
+                                       c_batch_stride=S * D, ldc=D, gate=modv[mo + 5 * D:], resid=x_img, ldg=LM),
+                   "cw2", dict(a=hid_txt, out=x, bias=blk["cb2"], M=Mt, lda=F, c_rows_per_batch=St,
+                               c_batch_stride=S * D, ldc=D, gate=modv[cmo + 5 * D:], resid=x, ldg=LM))
+        if taps is not None:
+            taps[f"double.{i}"] = x[:nb].clone()
+
+    def _blocks_after_first(self, ws, nb, St, Si, cos, sin, taps):
+        """double blocks 1... and the single blocks on the first ``nb`` slots of the workspace"""
+        cfg = self.cfg
+        D, H, S, LM = cfg.dim, cfg.num_attention_heads, St + Si, self.mod_total
+        F = cfg.mlp_ratio * D
+        M = nb * S
+        x, nrm, qkv, vt, catb, modv = ws["x"], ws["nrm"], ws["qkv"], ws["vt"], ws["cat"], ws["mod"].view(-1)
+        scale = 1.0 / math.sqrt(cfg.attention_head_dim)
+        for i in range(1, len(self.double)):
+            self._double_block(ws, i, nb, St, Si, cos, sin, taps)
+
+        cat_mlp = catb.view(-1)[D:]
+        fused_qkv_mlp = (3 * D) % 256 == 0 and (_FUSED_QKV_MLP if _FUSED_QKV_MLP is not None else
+                                                ops.gemm_cost(M, 3 * D + F, D) * 10 <= (ops.gemm_cost(M, 3 * D, D) + ops.gemm_cost(M, F, D)) * 9)
+        mx_qkv, mx_mlp, mx_out = self._mx_moves(3 * D, D), self._mx_moves(F, D), self._mx_moves(D, D + F)
+        for i, blk in enumerate(self.single):
+            mo = self.mod_off[("s", i)]      # shift, scale, gate
+            ops.layernorm(x, nrm, M, D, scale=modv[mo + D:], shift=modv[mo:], ldx=D, ld_mod=LM, rows_per_batch=S,
+                          x_batch_stride=S * D)
+            if mx_qkv or mx_mlp:
+                # one quantisation of the modulated LayerNorm output serves q|k|v and proj_mlp: two launches over the stacked weight's row
+                # ranges (a range whose shape stays on bf16 takes the bf16 GEMM)
+                qa = self._mx_quant(ws, nrm, M, D, D)
+                wq, wsc = blk["wqkvm@mx"]
+                for moves, lo, hi, dst, ldd, act_ in ((mx_qkv, 0, 3 * D, qkv, 3 * D, ops.ACT_NONE), (mx_mlp, 3 * D, 3 * D + F, cat_mlp, D + F, ops.ACT_GELU_TANH)):
+                    if moves:
+                        ops.gemm_mxfp8(qa[0], qa[1], wq[lo:hi], wsc[lo:hi], dst, bias=blk["bqkvm"][lo:hi], act=act_, M=M, ldc=ldd)
+                    else:
+                        ops.gemm(nrm, blk["wqkvm"][lo:hi], out=dst, bias=blk["bqkvm"][lo:hi], act=act_, M=M, lda=D, ldc=ldd)
+            elif fused_qkv_mlp:
+                ops.gemm(nrm, blk["wqkvm"], out=qkv, bias=blk["bqkvm"], act=ops.ACT_GELU_TANH, act_n0=3 * D, M=M, lda=D, ldc=3 * D,
+                         out2=cat_mlp, ldc2=D + F, n_split=3 * D)
+            else:       # (test-sized widths whose q|k|v block does not end on a tile boundary)
+                ops.gemm(nrm, blk["wqkvm"][: 3 * D], out=qkv, bias=blk["bqkvm"][: 3 * D], M=M, lda=D, ldc=3 * D)
+                ops.gemm(nrm, blk["wqkvm"][3 * D:], out=cat_mlp, bias=blk["bqkvm"][3 * D:], act=ops.ACT_GELU_TANH, M=M, lda=D, ldc=D + F)
+            if _SEPARATE_QPREP:
+                ops.qk_norm_rope_vt(qkv, vt, blk["nq"], blk["nk"], blk["nq"], blk["nk"], cos, sin, nb, S, H, 3 * D, 0)
+                ops.attention(qkv, qkv.view(-1)[D:], vt, catb, nb, S, H, 3 * D, S * 3 * D, D + F, S * (D + F), scale)
+            else:
+                ops.k_norm_rope_vt(qkv, vt, blk["nk"], blk["nk"], cos, sin, nb, S, H, 3 * D, 0)
+                ops.attention_qprep(qkv, qkv.view(-1)[D:], vt, catb, nb, S, H, 3 * D, S * 3 * D, D + F, S * (D + F), scale,
+                                    blk["nq"], blk["nq"], cos, sin, 0)
+            proj = dict(a=catb, out=x, bias=blk["bo"], M=M, lda=D + F, c_rows_per_batch=S, c_batch_stride=S * D,
+                        ldc=D, gate=modv[mo + 2 * D:], resid=x, ldg=LM)
+            if mx_out:
+                self._mx_gemm(ws, proj, blk["wo@mx"])
+            else:
+                ops.gemm(proj.pop("a"), blk["wo"], **proj)
+            if taps is not None:
+                taps[f"single.{i}"] = x[:nb].clone()
+
     def forward(self, hidden, enc, pooled, timestep, img_ids, txt_ids, guidance=None, taps: dict | None = None,
                 cache: StepCache | None = None):
         """hidden bf16 [B, S_img, in]; enc bf16 [B, S_txt, J]; pooled bf16 [B, P]; timestep / guidance
         fp32 [B] host or device; returns bf16 [B, S_img, out] (a view of an internal workspace).
         ``cache``: a :class:`StepCache` (opt-in; None is the plain forward, the same launches in the same order): the first double block
-        runs, then the step either reuses the cached residual of the remaining blocks or computes them and refreshes the cache."""
+        runs, then the step either reuses the cached residual of the remaining blocks or computes them and refreshes the cache.  Under
+        the cache's scope "image" a step on which only some images reuse runs the remaining blocks at the batch size of the others, on the
+        same workspace with those images swapped to its front; a step on which all or none reuse launches what scope "batch" launches."""
         cfg = self.cfg
         if cache is not None and (cfg.num_layers < 1 or cfg.num_layers + cfg.num_single_layers < 2):
             raise ValueError("a step cache needs a double block and at least one further block")
-        reused = False
-        D, H = cfg.dim, cfg.num_attention_heads
+        D = cfg.dim
         F = cfg.mlp_ratio * D
         B, Si, _ = hidden.shape
         St = enc.shape[1]
         S = St + Si
         ws = self._workspace(B, St, Si)
-        x, nrm, qkv, vt, attn, catb, mod = ws["x"], ws["nrm"], ws["qkv"], ws["vt"], ws["attn"], ws["cat"], ws["mod"]
+        x, nrm, mod = ws["x"], ws["nrm"], ws["mod"]
         if "mxq" not in ws and any(self._mx_moves(n, k) for n, k in ((3 * D, D), (D, D), (F, D), (D, F), (D, D + F))):
             # the widest Linear input (the single blocks' [attn | mlp], D + F columns) as e4m3 bytes + its e8m0 scales
             ws["mxq"] = torch.empty(B * S * (D + F), dtype=torch.uint8, device=self.device)
             ws["mxs"] = torch.empty(B * S * (D + F) // 32, dtype=torch.uint8, device=self.device)
         cos, sin = self._rope(txt_ids, img_ids)
         hidden = hidden.contiguous(); enc = enc.contiguous(); pooled = pooled.contiguous()
-        Mi, Mt, M = B * Si, B * St, B * S
+        Mi, Mt = B * Si, B * St
         x_img = x.view(-1)[St * D:]          # joint buffer, image rows of batch 0 onwards
-        scale = 1.0 / math.sqrt(cfg.attention_head_dim)
 
         # embedders write straight into the joint buffer
         ops.gemm(hidden.view(Mi, -1), self.w["x_embedder.weight"], out=x_img, bias=self.w["x_embedder.bias"], M=Mi,
@@ -404,109 +587,55 @@ class FluxTransformerHIP:
             taps["x_embed"] = x[:, St:].clone(); taps["ctx_embed"] = x[:, :St].clone()
 
         nrm_img = nrm.view(-1)[: Mi * D]
-        nrm_txt = nrm.view(-1)[Mi * D: (Mi + Mt) * D]
-        qkv_img = qkv.view(-1)[St * 3 * D:]
-        attn_img = attn.view(-1)[St * D:]
-        hid = catb.view(-1)                   # MLP hidden scratch for double blocks: image rows, then text rows
-        hid_txt = hid[Mi * F:]
-
-        for i, blk in enumerate(self.double):
-            mo, cmo = self.mod_off[(i, "norm1")], self.mod_off[(i, "norm1_context")]
-            if cache is not None and i == 0:      # step cache, hook 1: the image rows as block 0 receives them
+        nb, computing, pairs = B, None, ()      # the batch blocks 1... run at; scope "image", mixed step: the computing images, the compaction
+        if self.double:
+            if cache is not None:      # step cache, hook 1: the image rows as block 0 receives them
                 cache._prepare(B, Si, D, self._linear_precision, self.device)
                 cache.E.copy_(x[:, St:])
-            # chunk order: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
-            ops.layernorm(x_img, nrm_img, Mi, D, scale=modv[mo + D:], shift=modv[mo:], ldx=D, rows_per_batch=Si,
-                          x_batch_stride=S * D, ld_mod=LM)
-            ops.layernorm(x, nrm_txt, Mt, D, scale=modv[cmo + D:], shift=modv[cmo:], ldx=D, rows_per_batch=St,
-                          x_batch_stride=S * D, ld_mod=LM)
-            # the image-stream and text-stream Linears of a pair share N and K: one launch when they are small alone (ops.gemm_pair)
-            self._pair(ws, blk, "wqkv", dict(a=nrm_img, out=qkv_img, bias=blk["bqkv"], M=Mi, lda=D, c_rows_per_batch=Si,
-                                             c_batch_stride=S * 3 * D, ldc=3 * D),
-                       "cwqkv", dict(a=nrm_txt, out=qkv, bias=blk["cbqkv"], M=Mt, lda=D, c_rows_per_batch=St,
-                                     c_batch_stride=S * 3 * D, ldc=3 * D))
-            if _SEPARATE_QPREP:     # A/B switch: the round-1 route (q prepared by the pass, plain attention)
-                ops.qk_norm_rope_vt(qkv, vt, blk["cnq"], blk["cnk"], blk["nq"], blk["nk"], cos, sin, B, S, H, 3 * D, St)
-                ops.attention(qkv, qkv.view(-1)[D:], vt, attn, B, S, H, 3 * D, S * 3 * D, D, S * D, scale)
-            else:
-                # k: RMSNorm + RoPE in place, V -> V^T; q: norm_q / norm_added_q + RoPE inside the attention kernel's Q load
-                ops.k_norm_rope_vt(qkv, vt, blk["cnk"], blk["nk"], cos, sin, B, S, H, 3 * D, St)
-                ops.attention_qprep(qkv, qkv.view(-1)[D:], vt, attn, B, S, H, 3 * D, S * 3 * D, D, S * D, scale,
-                                    blk["cnq"], blk["nq"], cos, sin, St)
-            self._pair(ws, blk, "wo", dict(a=attn_img, out=x_img, bias=blk["bo"], M=Mi, a_rows_per_batch=Si, a_batch_stride=S * D,
-                                           lda=D, c_rows_per_batch=Si, c_batch_stride=S * D, ldc=D, gate=modv[mo + 2 * D:], resid=x_img, ldg=LM),
-                       "cwo", dict(a=attn, out=x, bias=blk["cbo"], M=Mt, a_rows_per_batch=St, a_batch_stride=S * D,
-                                   lda=D, c_rows_per_batch=St, c_batch_stride=S * D, ldc=D, gate=modv[cmo + 2 * D:], resid=x, ldg=LM))
-            # MLPs (the two streams are independent: both LayerNorms, both up-projections, both down-projections)
-            ops.layernorm(x_img, nrm_img, Mi, D, scale=modv[mo + 4 * D:], shift=modv[mo + 3 * D:], ldx=D,
-                          rows_per_batch=Si, x_batch_stride=S * D, ld_mod=LM)
-            ops.layernorm(x, nrm_txt, Mt, D, scale=modv[cmo + 4 * D:], shift=modv[cmo + 3 * D:], ldx=D,
-                          rows_per_batch=St, x_batch_stride=S * D, ld_mod=LM)
-            self._pair(ws, blk, "w1", dict(a=nrm_img, out=hid, bias=blk["b1"], act=ops.ACT_GELU_TANH, M=Mi, lda=D, ldc=F),
-                       "cw1", dict(a=nrm_txt, out=hid_txt, bias=blk["cb1"], act=ops.ACT_GELU_TANH, M=Mt, lda=D, ldc=F))
-            self._pair(ws, blk, "w2", dict(a=hid, out=x_img, bias=blk["b2"], M=Mi, lda=F, c_rows_per_batch=Si,
-                                           c_batch_stride=S * D, ldc=D, gate=modv[mo + 5 * D:], resid=x_img, ldg=LM),
-                       "cw2", dict(a=hid_txt, out=x, bias=blk["cb2"], M=Mt, lda=F, c_rows_per_batch=St,
-                                   c_batch_stride=S * D, ldc=D, gate=modv[cmo + 5 * D:], resid=x, ldg=LM))
-            if taps is not None:
-                taps[f"double.{i}"] = x.clone()
-            if cache is not None and i == 0:
+            self._double_block(ws, 0, B, St, Si, cos, sin, taps)
+            if cache is not None:
                 # step cache, hook 2: E <- block 0's residual of the image rows, its ratio against the last computed step's (F), the decision
-                ops.stepcache_delta(x_img, cache.E, cache.F if cache.valid else None, cache.ratios, cache.workspace, B, Si, D, S * D)
+                ops.stepcache_delta(x_img, cache.E, cache.F if any(cache.valid_images) else None, cache.ratios, cache.workspace, B, Si, D, S * D)
                 if taps is not None:
                     taps["cache.delta"] = cache.E.clone()
-                reused = cache._decide()
-                if reused:      # add that step's residual of the remaining blocks and go to the final LayerNorm; F and R stay
+                mask = cache._decide()
+                if all(mask):      # add that step's residual of the remaining blocks and go to the final LayerNorm; F and R stay
                     ops.stepcache_apply(x_img, cache.R, B, Si, D, S * D, +1)
                     if taps is not None:
                         taps["cache.x_img"] = x[:, St:].clone()
-                    break
-                # hook 3, computed step: this residual becomes F; R <- the image rows now, turned into the residual after the last block
-                cache.E, cache.F = cache.F, cache.E
-                cache.valid = False
-                cache.R.copy_(x[:, St:])
-
-        cat_mlp = catb.view(-1)[D:]
-        fused_qkv_mlp = (3 * D) % 256 == 0 and (_FUSED_QKV_MLP if _FUSED_QKV_MLP is not None else
-                                                ops.gemm_cost(M, 3 * D + F, D) * 10 <= (ops.gemm_cost(M, 3 * D, D) + ops.gemm_cost(M, F, D)) * 9)
-        mx_qkv, mx_mlp, mx_out = self._mx_moves(3 * D, D), self._mx_moves(F, D), self._mx_moves(D, D + F)
-        for i, blk in enumerate(() if reused else self.single):
-            mo = self.mod_off[("s", i)]      # shift, scale, gate
-            ops.layernorm(x, nrm, M, D, scale=modv[mo + D:], shift=modv[mo:], ldx=D, ld_mod=LM, rows_per_batch=S,
-                          x_batch_stride=S * D)
-            if mx_qkv or mx_mlp:
-                # one quantisation of the modulated LayerNorm output serves q|k|v and proj_mlp: two launches over the stacked weight's row
-                # ranges (a range whose shape stays on bf16 takes the bf16 GEMM)
-                qa = self._mx_quant(ws, nrm, M, D, D)
-                wq, wsc = blk["wqkvm@mx"]
-                for moves, lo, hi, dst, ldd, act_ in ((mx_qkv, 0, 3 * D, qkv, 3 * D, ops.ACT_NONE), (mx_mlp, 3 * D, 3 * D + F, cat_mlp, D + F, ops.ACT_GELU_TANH)):
-                    if moves:
-                        ops.gemm_mxfp8(qa[0], qa[1], wq[lo:hi], wsc[lo:hi], dst, bias=blk["bqkvm"][lo:hi], act=act_, M=M, ldc=ldd)
-                    else:
-                        ops.gemm(nrm, blk["wqkvm"][lo:hi], out=dst, bias=blk["bqkvm"][lo:hi], act=act_, M=M, lda=D, ldc=ldd)
-            elif fused_qkv_mlp:
-                ops.gemm(nrm, blk["wqkvm"], out=qkv, bias=blk["bqkvm"], act=ops.ACT_GELU_TANH, act_n0=3 * D, M=M, lda=D, ldc=3 * D,
-                         out2=cat_mlp, ldc2=D + F, n_split=3 * D)
-            else:       # (test-sized widths whose q|k|v block does not end on a tile boundary)
-                ops.gemm(nrm, blk["wqkvm"][: 3 * D], out=qkv, bias=blk["bqkvm"][: 3 * D], M=M, lda=D, ldc=3 * D)
-                ops.gemm(nrm, blk["wqkvm"][3 * D:], out=cat_mlp, bias=blk["bqkvm"][3 * D:], act=ops.ACT_GELU_TANH, M=M, lda=D, ldc=D + F)
-            if _SEPARATE_QPREP:
-                ops.qk_norm_rope_vt(qkv, vt, blk["nq"], blk["nk"], blk["nq"], blk["nk"], cos, sin, B, S, H, 3 * D, 0)
-                ops.attention(qkv, qkv.view(-1)[D:], vt, catb, B, S, H, 3 * D, S * 3 * D, D + F, S * (D + F), scale)
-            else:
-                ops.k_norm_rope_vt(qkv, vt, blk["nk"], blk["nk"], cos, sin, B, S, H, 3 * D, 0)
-                ops.attention_qprep(qkv, qkv.view(-1)[D:], vt, catb, B, S, H, 3 * D, S * 3 * D, D + F, S * (D + F), scale,
-                                    blk["nq"], blk["nq"], cos, sin, 0)
-            proj = dict(a=catb, out=x, bias=blk["bo"], M=M, lda=D + F, c_rows_per_batch=S, c_batch_stride=S * D,
-                        ldc=D, gate=modv[mo + 2 * D:], resid=x, ldg=LM)
-            if mx_out:
-                self._mx_gemm(ws, proj, blk["wo@mx"])
-            else:
-                ops.gemm(proj.pop("a"), blk["wo"], **proj)
-            if taps is not None:
-                taps[f"single.{i}"] = x.clone()
-
-        if cache is not None and not reused:
+                    nb = 0
+                elif not any(mask):
+                    # hook 3, computed step: this residual becomes F; R <- the image rows now, turned into the residual after the last block
+                    cache.E, cache.F = cache.F, cache.E
+                    cache.valid = False
+                    cache.R.copy_(x[:, St:])
+                else:
+                    # scope "image", some images reuse: hook 3 for the computing images, the reuse for the others, then the computing
+                    # images go to the front of the batch (whole joint rows and their modulation rows)
+                    computing = [b for b in range(B) if not mask[b]]
+                    ops.stepcache_copy_images(cache.F, cache.E, Si * D, B, Si, D, computing)
+                    ops.stepcache_copy_images(cache.R, x_img, S * D, B, Si, D, computing)
+                    ops.stepcache_apply_images(x_img, cache.R, B, Si, D, S * D, +1, [b for b in range(B) if mask[b]])
+                    for b in computing:
+                        cache.valid_images[b] = False
+                    nb, pairs = compact_pairs(mask)
+                    ops.stepcache_swap(x, B, S, D, S * D, pairs)
+                    ops.stepcache_swap(mod, B, 1, LM, LM, pairs)
+                    if taps is not None:
+                        slots = list(range(B))
+                        for a, b in pairs:
+                            slots[a], slots[b] = slots[b], slots[a]
+                        taps["cache.slots"] = tuple(slots)      # the image each slot holds while blocks 1... run
+        if nb:
+            self._blocks_after_first(ws, nb, St, Si, cos, sin, taps)
+        if computing is not None:
+            # the tail runs at batch B in the batch's own order: it reads the image rows and norm_out's modulation, not the text rows
+            ops.stepcache_swap(x_img, B, Si, D, S * D, pairs)
+            ops.stepcache_swap(mod, B, 1, LM, LM, pairs)
+            ops.stepcache_apply_images(x_img, cache.R, B, Si, D, S * D, -1, computing)      # capture, per image
+            for b in computing:
+                cache.valid_images[b] = True
+        elif cache is not None and nb:
             ops.stepcache_apply(x_img, cache.R, B, Si, D, S * D, -1)      # capture: R <- x_img - (x_img after block 0)
             cache.valid = True
         mo = self.mod_off["out"]             # AdaLayerNormContinuous: scale, shift

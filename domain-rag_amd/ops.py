@@ -554,6 +554,53 @@ def stepcache_apply(x: torch.Tensor, r: torch.Tensor, B: int, rows_per_batch: in
     check(lib.drag_stepcache_apply_bf16(_p(x), _p(r), B, rows_per_batch, cols, x_batch_stride, sign, _stream()), "drag_stepcache_apply_bf16")
 
 
+def _index_list(values) -> tuple:
+    """a host list of image indices as the C array the list forms take (the library validates range, order and length), and its length"""
+    v = [int(i) for i in values]
+    return (ctypes.c_int32 * max(1, len(v)))(*v), len(v)
+
+
+def stepcache_swap(x: torch.Tensor, B: int, rows_per_batch: int, cols: int, x_batch_stride: int, pairs) -> None:
+    """exchange in place the ``rows_per_batch`` x ``cols`` elements of image ``a`` with those of image ``b`` for every ``(a, b)`` of
+    ``pairs`` (host integers, disjoint, at most 32 pairs), one launch (``drag_stepcache_swap_bf16``); ``x`` addressed as in
+    ``stepcache_delta``.  No pairs: nothing is launched."""
+    lib = _lib.load()
+    _need(x, torch.bfloat16, "stepcache_swap.x")
+    flat = []
+    for pair in pairs:
+        a, b = pair
+        flat += [a, b]
+    arr, n = _index_list(flat)
+    _stepcache_room(x, {}, B, rows_per_batch, cols, x_batch_stride, "stepcache_swap")
+    check(lib.drag_stepcache_swap_bf16(_p(x), B, rows_per_batch, cols, x_batch_stride, arr, n // 2, _stream()), "drag_stepcache_swap_bf16")
+
+
+def stepcache_apply_images(x: torch.Tensor, r: torch.Tensor, B: int, rows_per_batch: int, cols: int, x_batch_stride: int, sign: int,
+                           images) -> None:
+    """``stepcache_apply`` on the images listed in ``images`` only (host integers, strictly increasing, at most 64): the same arithmetic
+    per element, ``r`` indexed by image (``drag_stepcache_apply_images_bf16``).  An empty list launches nothing."""
+    lib = _lib.load()
+    _need(x, torch.bfloat16, "stepcache_apply_images.x")
+    _need(r, torch.bfloat16, "stepcache_apply_images.r")
+    arr, n = _index_list(images)
+    _stepcache_room(x, dict(r=r), B, rows_per_batch, cols, x_batch_stride, "stepcache_apply_images")
+    check(lib.drag_stepcache_apply_images_bf16(_p(x), _p(r), B, rows_per_batch, cols, x_batch_stride, sign, arr, n, _stream()),
+          "drag_stepcache_apply_images_bf16")
+
+
+def stepcache_copy_images(dst: torch.Tensor, src: torch.Tensor, src_batch_stride: int, B: int, rows_per_batch: int, cols: int,
+                          images) -> None:
+    """``dst[b] <- src[b]`` for the images listed in ``images`` (as in ``stepcache_apply_images``): ``dst`` dense [B, rows_per_batch, cols],
+    image ``b`` of ``src`` at ``src + b * src_batch_stride`` (``drag_stepcache_copy_images_bf16``)."""
+    lib = _lib.load()
+    _need(dst, torch.bfloat16, "stepcache_copy_images.dst")
+    _need(src, torch.bfloat16, "stepcache_copy_images.src")
+    arr, n = _index_list(images)
+    _stepcache_room(src, dict(dst=dst), B, rows_per_batch, cols, src_batch_stride, "stepcache_copy_images")
+    check(lib.drag_stepcache_copy_images_bf16(_p(dst), _p(src), src_batch_stride, B, rows_per_batch, cols, arr, n, _stream()),
+          "drag_stepcache_copy_images_bf16")
+
+
 def act(x: torch.Tensor, kind: int, out: torch.Tensor | None = None) -> torch.Tensor:
     lib = _lib.load()
     _need(x, torch.bfloat16, "x")

@@ -283,7 +283,7 @@ int drag_layernorm_modulate_bf16(const void* x, void* y, const void* scale, cons
                                  int32_t ldy, int32_t ld_mod, float eps, void* stream);
 
 /* ---------------------------------------------------------------------------------------
- * First-block step cache of the Flux DiT (opt-in; the default forward calls neither of these).  Both address the image rows of the joint
+ * First-block step cache of the Flux DiT (opt-in; the default forward calls none of these).  The first two address the image rows of the joint
  * activation buffer as drag_layernorm_modulate_bf16 does: batch b's rows_per_batch rows of cols bf16 elements (row stride cols) start at
  * x + b * x_batch_stride; e, f and r are dense [B, rows_per_batch, cols].  Both validate before the launch (null pointers, cols % 8,
  * x_batch_stride < rows_per_batch * cols, 16-byte alignment): a refused call returns -1 and launches nothing.
@@ -300,6 +300,24 @@ int drag_stepcache_delta_bf16(const void* x, void* e, const void* f, double* rat
  * sign = -1, the capture form: r <- bf16(f32(x) - f32(r)), r holding a saved copy of the earlier x. */
 int drag_stepcache_apply_bf16(void* x, void* r, int32_t B, int32_t rows_per_batch, int32_t cols, int64_t x_batch_stride, int32_t sign,
                               void* stream);
+/* The list forms (StepCache scope "image": every image of the batch decides for itself whether it reuses).  They address x and validate
+ * as the two above.  An image list (`images`, n_images entries) or a pair list (`pairs`, 2 * n_pairs entries) is a HOST array: the call
+ * copies it into the kernel's argument struct — at most 64 indices, more is refused — after checking that every index lies in [0, B), that
+ * an image list is strictly increasing and that the indices of a pair list are all distinct (disjoint pairs), so no out-of-range index
+ * reaches a kernel.  An empty list is a successful no-op without a launch.
+ *
+ * drag_stepcache_swap_bf16 — exchanges in place the rows_per_batch x cols elements of image pairs[2i] with those of image pairs[2i + 1],
+ *   all pairs in one launch; nothing outside those rows is touched (the compaction of the computing images to the front of the batch).
+ * drag_stepcache_apply_images_bf16 — drag_stepcache_apply_bf16 on the listed images only, the same arithmetic and rounding per element;
+ *   r stays indexed by image.
+ * drag_stepcache_copy_images_bf16 — dst_dense[b] <- src[b] for the listed images b: dst_dense is [B, rows_per_batch, cols], image b of
+ *   src starts at src + b * src_batch_stride (the joint buffer, or another dense buffer with src_batch_stride = rows_per_batch * cols). */
+int drag_stepcache_swap_bf16(void* x, int32_t B, int32_t rows_per_batch, int32_t cols, int64_t x_batch_stride, const int32_t* pairs,
+                             int32_t n_pairs, void* stream);
+int drag_stepcache_apply_images_bf16(void* x, void* r, int32_t B, int32_t rows_per_batch, int32_t cols, int64_t x_batch_stride,
+                                     int32_t sign, const int32_t* images, int32_t n_images, void* stream);
+int drag_stepcache_copy_images_bf16(void* dst_dense, const void* src, int64_t src_batch_stride, int32_t B, int32_t rows_per_batch,
+                                    int32_t cols, const int32_t* images, int32_t n_images, void* stream);
 
 /* elementwise helpers (bf16) */
 int drag_act_bf16(const void* x, void* y, int64_t n, int32_t act, void* stream);

@@ -267,6 +267,7 @@ def _hip_pipes(args, kind, encoders):
     pipe = cls.from_pretrained(flux).to("cuda")
     if getattr(args, "step_cache", None):       # --step-cache: the HIP side runs with the first-block step cache (flux.StepCache)
         pipe.pipe.step_cache = args.step_cache
+        pipe.pipe.step_cache_scope = getattr(args, "step_cache_scope", None) or "batch"
     return prior, pipe
 
 
@@ -356,6 +357,8 @@ def main(argv=None) -> int:
     ap.add_argument("--out", default="accept_report.json")
     ap.add_argument("--step-cache", type=float, default=None, metavar="THRESHOLD",
                     help="run the HIP stage-2 / stage-3 pipelines with the first-block step cache at this threshold (default: off)")
+    ap.add_argument("--step-cache-scope", choices=["batch", "image"], default="batch",
+                    help="with --step-cache: the batch decides a reuse as a whole, or every image for itself (default: batch)")
     args = ap.parse_args(argv)
     sections = [s for s in args.sections.split(",") if s]
     bad = [s for s in sections if s not in SECTIONS]
@@ -366,6 +369,8 @@ def main(argv=None) -> int:
                                                              "topk": "indices bit-exact"}, "missing": info["missing"]}
     if args.step_cache:
         report["step_cache"] = args.step_cache
+        if args.step_cache_scope == "image":
+            report["step_cache_scope"] = args.step_cache_scope
     if any(s in sections for s in ("stage2", "stage3")) and not args.target:
         report["missing"].append("--target <inpainted k-shot image>")
     if report["missing"]:

@@ -11,7 +11,13 @@ Per pass: wall time per batch, GPU time of a computed and of a reused step (even
 trace, and the distance of its result from the off pass (rms of the final packed latents, mean absolute uint8 level).  The two kernels are
 also timed alone at the workload's shape.  The weights are seeded random: the ratios and distances say nothing about real checkpoints.
 
-    python scripts/bench_step_cache.py [--out-dir profiles]      # writes step_cache.json and step_cache.log there"""
+    python scripts/bench_step_cache.py [--out-dir profiles]      # writes step_cache.json and step_cache.log there
+
+``--scope image`` measures the cache's scope "image" instead (every image decides for itself; a step on which k of B images compute runs
+the remaining blocks at batch k): per step, a forced pattern in which the LAST k images compute (the most swaps) under scope "image"
+against the same pattern under scope "batch", where any computing image makes all B compute.  Passes k = 0, B/4, B/2, 3B/4, B under
+"image" and k = 0, B under "batch", interleaved round by round in one process; the swaps and list kernels of a mixed step are also timed
+alone.  Writes step_cache_image.json and step_cache_image.log."""
 import argparse
 import json
 import math
@@ -35,7 +41,10 @@ def main(argv=None):
     ap.add_argument("--denoise-steps", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=2, help="timed rounds; every round runs each pass once, in order (one warm-up round first)")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
+    ap.add_argument("--scope", choices=["batch", "image"], default="batch", help="image: measure mixed steps of the cache's scope \"image\"")
     args = ap.parse_args(argv)
+    if args.scope == "image":
+        return main_image(args)
     dev = torch.device("cuda:0")
     n = args.denoise_steps
     job = SyntheticFillJob(batch=args.batch, res=args.res, denoise_steps=n, device=dev)
@@ -153,6 +162,121 @@ def main(argv=None):
         if d:
             say(f"{name:18s} " + " ".join("  -  " if x.ratios is None else f"{max(x.ratios):5.3f}" for x in d))
     with open(os.path.join(args.out_dir, "step_cache.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+        f.write("\n")
+    log.close()
+
+
+def main_image(args):
+    from domain_rag_amd.flux import compact_pairs
+    dev = torch.device("cuda:0")
+    n, B = args.denoise_steps, args.batch
+    job = SyntheticFillJob(batch=B, res=args.res, denoise_steps=n, device=dev)
+    ks = sorted({0, B // 4, B // 2, 3 * B // 4, B})
+    # pass -> (scope, k): from step 1 on the last k images compute; under "batch" any computing image makes all compute
+    passes = {"batch_k0": ("batch", 0), f"batch_k{B}": ("batch", B)}
+    passes.update({f"image_k{k}": ("image", k) for k in ks})
+    os.makedirs(args.out_dir, exist_ok=True)
+    log = open(os.path.join(args.out_dir, "step_cache_image.log"), "w")
+
+    def say(s=""):
+        print(s, flush=True)
+        log.write(s + "\n"); log.flush()
+
+    def run(name):
+        scope, k = passes[name]
+        mask = tuple(b < B - k for b in range(B))          # True = reuses
+        job.fill.step_cache, job.fill.step_cache_scope = math.inf, scope
+        job.fill.step_cache_forced = [False] + [k == 0] * (n - 1) if scope == "batch" else None
+        job.fill.step_cache_forced_images = [(False,) * B] + [mask] * (n - 1) if scope == "image" else None
+        marks = []
+
+        def on_step(i, latents):
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            marks.append(ev)
+        pe, pp = job.prior(job.bg, job.t5, job.pooled, [job.ips], [1.0], group=1)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        job.fill(job.image, job.mask, pe, pp, guidance_scale=job.guidance, num_inference_steps=n, strength=job.strength,
+                 enc_noise=job.enc_noise, masked_enc_noise=job.menc_noise, noise_tokens=job.noise_tokens, on_step=on_step)
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        got = job.fill.last_step_reused_images
+        want = [(False,) * B] + [mask if scope == "image" else (k == 0,) * B] * (n - 1)
+        assert got == want, (name, got)
+        # steps 2 ... n - 1: the forced pattern in its steady state (step 0 also holds the VAE encodes, step 1 follows the all-compute step)
+        return dict(wall_s=wall, step_ms=[marks[i - 1].elapsed_time(marks[i]) for i in range(2, len(marks))])
+
+    say(f"# bench_step_cache --scope image: B = {B}, {args.res}^2, {n} steps, {args.rounds} timed rounds after one warm-up round; seeded random weights")
+    say(f"# device: {torch.cuda.get_device_name(0)}")
+    say("# per pass and round: median GPU time of a step of the forced pattern (steps 2 ... n - 1), wall per batch")
+    results = {name: [] for name in passes}
+    for rnd in range(args.rounds + 1):
+        for name in passes:
+            r = run(name)
+            if rnd == 0:
+                continue
+            results[name].append(r)
+            say(f"round {rnd} {name:10s} step {statistics.median(r['step_ms']):8.2f} ms median (min {min(r['step_ms']):8.2f}, max {max(r['step_ms']):8.2f})"
+                f"  wall {r['wall_s']:7.3f} s/batch")
+
+    # ---- the swaps and list kernels of one mixed step alone, at the workload's shape
+    Si, St, D, LM = job.Si, job.St, job.cfg.dim, job.fill.tr.mod_total
+    S = St + Si
+    x = torch.randn((B, S, D), device=dev).bfloat16()
+    mod = torch.randn((B, LM), device=dev).bfloat16()
+    E, F, R = (torch.randn((B, Si, D), device=dev).bfloat16() for _ in range(3))
+    x_img = x.view(-1)[St * D:]
+
+    def timed(fn, reps=20):
+        for _ in range(3):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3
+    kern = {}
+    say()
+    say(f"# kernels of a mixed step alone (us), B = {B}, {Si} x {D} image rows + {St} text rows per image, modulation rows of {LM}")
+    for k in [k for k in ks if 0 < k < B]:
+        mask = tuple(b < B - k for b in range(B))
+        C, U = [b for b in range(B) if not mask[b]], [b for b in range(B) if mask[b]]
+        _, pairs = compact_pairs(mask)
+        kern[k] = {"copy_images E -> F (computing)": timed(lambda: ops.stepcache_copy_images(F, E, Si * D, B, Si, D, C)),
+                   "copy_images x_img -> R (computing)": timed(lambda: ops.stepcache_copy_images(R, x_img, S * D, B, Si, D, C)),
+                   "apply_images +1 (reusing)": timed(lambda: ops.stepcache_apply_images(x_img, R, B, Si, D, S * D, +1, U)),
+                   "swap x, joint rows": timed(lambda: ops.stepcache_swap(x, B, S, D, S * D, pairs)),
+                   "swap mod (twice per step)": timed(lambda: ops.stepcache_swap(mod, B, 1, LM, LM, pairs)),
+                   "swap x back, image rows": timed(lambda: ops.stepcache_swap(x_img, B, Si, D, S * D, pairs)),
+                   "apply_images -1 (computing)": timed(lambda: ops.stepcache_apply_images(x_img, R, B, Si, D, S * D, -1, C))}
+        total = sum(kern[k].values()) + kern[k]["swap mod (twice per step)"]
+        kern[k]["total per mixed step"] = total
+        say(f"k = {k} ({len(pairs)} pairs): " + "; ".join(f"{name} {us:.1f}" for name, us in kern[k].items()))
+    whole = {"R.copy_(x_img) of a computed step": timed(lambda: R.copy_(x[:, St:])),
+             "apply -1 of a computed step": timed(lambda: ops.stepcache_apply(x_img, R, B, Si, D, S * D, -1)),
+             "apply +1 of a reused step": timed(lambda: ops.stepcache_apply(x_img, R, B, Si, D, S * D, +1))}
+    say("whole-batch counterparts: " + "; ".join(f"{name} {us:.1f}" for name, us in whole.items()))
+
+    # ---- summary
+    def steps(name):
+        return [t for r in results[name] for t in r["step_ms"]]
+    summary = {"config": dict(batch=B, res=args.res, denoise_steps=n, rounds=args.rounds, device=torch.cuda.get_device_name(0), weights="seeded random"),
+               "passes": {name: dict(scope=passes[name][0], computing_images=passes[name][1], step_ms_median_per_round=[statistics.median(r["step_ms"]) for r in results[name]],
+                                     step_ms_median=statistics.median(steps(name)), step_ms_min=min(steps(name)), step_ms_max=max(steps(name)),
+                                     wall_s_per_batch=[r["wall_s"] for r in results[name]]) for name in passes},
+               "mixed_step_kernels_us": {str(k): v for k, v in kern.items()}, "whole_batch_kernels_us": whole}
+    say()
+    say("# summary: median step over all timed rounds; image_k vs the all-compute step of scope batch, round by round")
+    full = f"batch_k{B}"
+    for name in passes:
+        per_round = [statistics.median(r["step_ms"]) / statistics.median(f["step_ms"]) for r, f in zip(results[name], results[full])]
+        summary["passes"][name]["vs_all_compute_per_round"] = per_round
+        say(f"{name:10s} {statistics.median(steps(name)):8.2f} ms  (x all-compute, per round: " + ", ".join(f"{v:.3f}" for v in per_round) + ")")
+    with open(os.path.join(args.out_dir, "step_cache_image.json"), "w") as f:
         json.dump(summary, f, indent=1)
         f.write("\n")
     log.close()
