@@ -277,10 +277,12 @@ extern "C" int drag_layernorm_modulate_bf16(const void* x, void* y, const void* 
                                             int32_t rows_per_batch, int64_t x_batch_stride, int32_t ldy,
                                             int32_t ld_mod, float eps, void* stream) {
   DRAG_CHECK(x && y, "drag_layernorm_modulate_bf16: null pointer");
-  DRAG_CHECK(M > 0 && D > 0 && D % 8 == 0 && D <= 64 * 8 * LN_MAX_IT, "drag_layernorm_modulate_bf16: D %% 8 == 0, D <= 4096");
+  DRAG_CHECK(M > 0 && D > 0 && D % 8 == 0 && D <= 64 * 8 * LN_MAX_IT, "drag_layernorm_modulate_bf16: D % 8 == 0, D <= 4096");
   DRAG_CHECK(ldx % 8 == 0 && ldy % 8 == 0 && ld_mod % 8 == 0, "drag_layernorm_modulate_bf16: strides must be multiples of 8");
   DRAG_CHECK((scale == nullptr) == (shift == nullptr) && (gamma == nullptr) == (beta == nullptr),
              "drag_layernorm_modulate_bf16: scale/shift and gamma/beta come in pairs");
+  // one form per call: the kernel would take gamma/beta and drop the modulation without a word
+  DRAG_CHECK(!(scale && gamma), "drag_layernorm_modulate_bf16: scale/shift and gamma/beta exclude each other");
   LnArgs p;
   p.x = (const bf16_t*)x; p.y = (bf16_t*)y;
   p.scale = (const bf16_t*)scale; p.shift = (const bf16_t*)shift;

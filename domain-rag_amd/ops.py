@@ -492,14 +492,51 @@ def attention_v(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Te
 def layernorm(x: torch.Tensor, y: torch.Tensor, M: int, D: int, *, scale=None, shift=None, gamma=None, beta=None,
               ldx: int | None = None, rows_per_batch: int = 0, x_batch_stride: int = 0, ldy: int | None = None,
               ld_mod: int = 0, eps: float = 1e-6) -> torch.Tensor:
+    """``y`` [M, D] rows of ``ldy`` = LayerNorm of M rows of ``x`` (``drag_layernorm_modulate_bf16``): row r is row r % rows_per_batch of batch
+    b = r // rows_per_batch (0 = one batch of M rows), at b * x_batch_stride + (r % rows_per_batch) * ldx.  With ``scale`` / ``shift`` (batch b's D
+    values at b * ld_mod) the AdaLN modulation, with ``gamma`` / ``beta`` [D] the affine form, with neither the bare normalisation."""
     lib = _lib.load()
     _need(x, torch.bfloat16, "x")
     _need(y, torch.bfloat16, "y")
-    check(lib.drag_layernorm_modulate_bf16(_p(x), _p(y), _p(scale), _p(shift), _p(gamma), _p(beta), M, D,
-                                           ldx if ldx is not None else D, rows_per_batch, x_batch_stride,
-                                           ldy if ldy is not None else D, ld_mod, eps, _stream()),
+    ldx = D if ldx is None else ldx
+    ldy = D if ldy is None else ldy
+    _layernorm_room(x, y, {"scale": scale, "shift": shift}, {"gamma": gamma, "beta": beta}, M, D, ldx, rows_per_batch, x_batch_stride, ldy,
+                    ld_mod)
+    check(lib.drag_layernorm_modulate_bf16(_p(x), _p(y), _p(scale), _p(shift), _p(gamma), _p(beta), M, D, ldx, rows_per_batch,
+                                           x_batch_stride, ldy, ld_mod, eps, _stream()),
           "drag_layernorm_modulate_bf16")
     return y
+
+
+def _layernorm_room(x: torch.Tensor, y: torch.Tensor, mods: dict, vecs: dict, M: int, D: int, ldx: int, rows_per_batch: int,
+                    x_batch_stride: int, ldy: int, ld_mod: int) -> None:
+    """``layernorm``'s operands before the launch: every optional one a GPU bf16 tensor, and the last element that the row addressing
+    reaches inside each operand's storage — a wrong stride is an error here, not a memory fault in the kernel (the shapes that the library
+    refuses, a bad D or a stride that is no multiple of 8, stay the library's to report)"""
+    for name, t in (*mods.items(), *vecs.items()):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.bfloat16):
+            raise ValueError(f"layernorm.{name}: expected a GPU bfloat16 tensor, got {getattr(t, 'dtype', type(t))}")
+    if M <= 0 or D <= 0:
+        return
+    for name, v in (("ldx", ldx), ("ldy", ldy), ("ld_mod", ld_mod), ("x_batch_stride", x_batch_stride)):
+        if v < 0:
+            raise ValueError(f"layernorm.{name}: {v} is negative")
+    rpb = rows_per_batch if rows_per_batch > 0 else M
+    b, s = divmod(M - 1, rpb)                               # the last row's batch and row in it
+    reach = b * x_batch_stride + s * ldx
+    if b > 0:                                               # a short last batch: the batch before it may reach further
+        reach = max(reach, (b - 1) * x_batch_stride + (rpb - 1) * ldx)
+    if reach + D > _room(x):
+        raise ValueError(f"layernorm.x: {M} rows of {D} (ldx {ldx}, {rpb} rows per batch, batch stride {x_batch_stride}) reach element "
+                         f"{reach + D} of {_room(x)} from its start")
+    if (M - 1) * ldy + D > _room(y):
+        raise ValueError(f"layernorm.y: {M} rows of {D} with ldy {ldy} do not fit ({_room(y)} elements from its start)")
+    for name, t in mods.items():
+        if t is not None and b * ld_mod + D > _room(t):
+            raise ValueError(f"layernorm.{name}: {b + 1} batches of {D} with ld_mod {ld_mod} do not fit ({_room(t)} elements from its start)")
+    for name, t in vecs.items():
+        if t is not None and D > _room(t):
+            raise ValueError(f"layernorm.{name}: expected at least {D} elements, got {_room(t)} from its start")
 
 
 def _stepcache_room(x: torch.Tensor, dense: dict, B: int, rows_per_batch: int, cols: int, x_batch_stride: int, what: str) -> None:
@@ -601,11 +638,31 @@ def stepcache_copy_images(dst: torch.Tensor, src: torch.Tensor, src_batch_stride
           "drag_stepcache_copy_images_bf16")
 
 
+def _dense_operand(t: torch.Tensor, n: int, name: str, exact: bool = False) -> None:
+    """a further operand of an elementwise kernel that walks ``n`` dense bf16 elements: a GPU bf16 tensor whose own ``n`` elements (at
+    least ``n``, or with ``exact`` just ``n``) lie dense in its storage — anything else is an error here, not a memory fault in the kernel"""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.bfloat16):
+        raise ValueError(f"{name}: expected a GPU bfloat16 tensor, got {getattr(t, 'dtype', type(t))}")
+    if not t.is_contiguous() or t.numel() < n or (exact and t.numel() != n):
+        raise ValueError(f"{name}: expected a contiguous tensor of {'' if exact else 'at least '}{n} elements, got shape {tuple(t.shape)}, "
+                         f"strides {t.stride()}")
+
+
+def _dense_first(x: torch.Tensor, name: str) -> None:
+    """the first operand sets the element count: its numel() elements must exist from its start on (an expanded view has fewer)"""
+    if x.numel() > _room(x):
+        raise ValueError(f"{name}: {x.numel()} elements, but only {_room(x)} from its start in its storage (an expanded view?)")
+
+
 def act(x: torch.Tensor, kind: int, out: torch.Tensor | None = None) -> torch.Tensor:
     lib = _lib.load()
     _need(x, torch.bfloat16, "x")
+    _dense_first(x, "act.x")
     if out is None:
         out = torch.empty_like(x)
+    _dense_operand(out, x.numel(), "act.out", exact=True)
+    if x.numel() == 0:                                      # an empty tensor has no address to hand the library
+        return out
     check(lib.drag_act_bf16(_p(x), _p(out), x.numel(), kind, _stream()), "drag_act_bf16")
     return out
 
@@ -621,15 +678,23 @@ def timestep_embedding(t: torch.Tensor, dim: int) -> torch.Tensor:
 def flow_euler_step(x: torch.Tensor, v: torch.Tensor, dt: float) -> None:
     lib = _lib.load()
     _need(x, torch.bfloat16, "x")
-    _need(v, torch.bfloat16, "v")
+    _dense_first(x, "flow_euler_step.x")
+    _dense_operand(v, x.numel(), "flow_euler_step.v")
+    if x.numel() == 0:
+        return
     check(lib.drag_flow_euler_step_bf16(_p(x), _p(v), dt, x.numel(), _stream()), "drag_flow_euler_step_bf16")
 
 
 def add(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     lib = _lib.load()
     _need(a, torch.bfloat16, "a")
+    _dense_first(a, "add.a")
+    _dense_operand(b, a.numel(), "add.b")
     if out is None:
         out = torch.empty_like(a)
+    _dense_operand(out, a.numel(), "add.out", exact=True)
+    if a.numel() == 0:
+        return out
     check(lib.drag_add_bf16(_p(a), _p(b), _p(out), a.numel(), _stream()), "drag_add_bf16")
     return out
 
@@ -638,6 +703,8 @@ def to_bf16(x: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     _need(x, torch.float32, "x")
     out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+    if x.numel() == 0:
+        return out
     check(lib.drag_cast_f32_to_bf16(_p(x), _p(out), x.numel(), _stream()), "drag_cast_f32_to_bf16")
     return out
 
@@ -646,6 +713,8 @@ def to_f32(x: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     _need(x, torch.bfloat16, "x")
     out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    if x.numel() == 0:
+        return out
     check(lib.drag_cast_bf16_to_f32(_p(x), _p(out), x.numel(), _stream()), "drag_cast_bf16_to_f32")
     return out
 

@@ -272,7 +272,8 @@ int drag_attention_bf16_choice(int32_t S, int32_t v_row_major, int32_t q_prep);
 const char* drag_attention_bf16_kernel_name(int32_t S, int32_t v_row_major, int32_t q_prep);
 
 /* drag_layernorm_modulate_bf16 — y = LN(x) * (1 + scale[b]) + shift[b]   (no affine LN, eps given)
- * or, with gamma/beta != NULL, y = LN(x) * gamma + beta (affine LayerNorm, scale/shift NULL).
+ * or, with gamma/beta != NULL, y = LN(x) * gamma + beta (affine LayerNorm, scale/shift NULL: both pairs at once are refused),
+ * or, with all four NULL, y = LN(x).
  * Replaces AdaLayerNormZero / AdaLayerNormZeroSingle / AdaLayerNormContinuous and nn.LayerNorm.
  *   x rows: batched-row addressing (rows_per_batch, x_batch_stride, ldx); y dense rows of ldy.
  *   scale, shift: bf16 [B, ld_mod] row b.

@@ -14,25 +14,8 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _ulps(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """distance in bf16 ulps between two bf16 tensors (ordered integer images of the bit patterns)"""
-    def ordered(x):
-        i = x.contiguous().view(torch.int16).to(torch.int32)
-        return torch.where(i < 0, -32768 - i, i)
-    return (ordered(a.cpu()) - ordered(b.cpu())).abs()
-
-
-def _bar(got, want, what, frac=0.99):
-    """equal on >= 99 % of the elements; every other one within 1 bf16 ulp, or — an output that cancels to near zero, where the kernel's fp32
-    accumulation and the float64 restatement part by more ulps than they part in value — within 2^-8 of the largest output"""
-    got, want = got.cpu(), want.cpu()
-    d = _ulps(got, want)
-    eq = (d == 0).float().mean().item()
-    err = (got.float() - want.float()).abs()
-    tol = 2.0 ** -8 * want.float().abs().max().item()
-    bad = (d > 1) & (err > tol)
-    assert eq >= frac and not bad.any(), f"{what}: {eq:.4%} equal, max {d.max().item()} ulp, worst abs err {err.max().item():.3e} (tol {tol:.3e})"
-    return eq
+sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+from bf16_bar import bar as _bar  # noqa: E402
 
 
 def _bf(x):
