@@ -1,0 +1,39 @@
+"""The flags stages 2 and 3 share, declared once, and the :class:`..engine.Engine` they describe (``--model_root`` stays with a stage's directory flags)."""
+from __future__ import annotations
+
+from ..engine import Engine
+from ..step_cache import parse_step_cache
+
+
+def add_engine_arguments(p, batch_flag: str, steps: int, tiny: str, png_files: str, png_note: str = "", own=()) -> None:
+    """``--synthetic-weights`` ... ``--png``.  ``batch_flag``: the stage's batch-size flag, which ``--step_cache``'s help names; ``tiny``, ``png_files``,
+    ``png_note``: the stage's words in those two helps; ``own``: (flag, add_argument keywords) of the stage's flags listed before ``--io_workers``"""
+    p.add_argument("--synthetic-weights", action="store_true")
+    p.add_argument("--tiny", action="store_true", help=f"test hook: tiny architectures, {tiny}")
+    p.add_argument("--linear_precision", choices=["bf16", "mxfp8"], default=None,
+                   help="the DiT blocks' Linears: bf16, or OCP MXFP8 operands on the block-scaled matrix instruction (opt-in, lower "
+                        "precision); default: $DRAG_LINEAR_PRECISION, else bf16")
+    p.add_argument("--step_cache", type=parse_step_cache, default=None, metavar="THRESHOLD",
+                   help="first-block step cache of the denoise loop (opt-in, lower fidelity): a step whose first-block residual moved by less "
+                        "than THRESHOLD (relative L1, every image of the batch) since the last computed step reuses that step's remaining "
+                        f"blocks; batch neighbours then influence a result (--step_cache_scope image or {batch_flag} 1 restores independence); "
+                        "default: $DRAG_STEP_CACHE, else off")
+    p.add_argument("--step_cache_scope", choices=["batch", "image"], default=None,
+                   help="who decides a reuse when --step_cache is on: batch = every image of the batch must be under the threshold; image = "
+                        "every image decides for itself and the remaining blocks run on the others only, so a result does not depend on its "
+                        "batch neighbours; default: $DRAG_STEP_CACHE_SCOPE, else batch")
+    p.add_argument("--text_encoder", choices=["transformers", "hip"], default="transformers",
+                   help="what encodes a prompt without a prompt_cache file: the transformers T5 / CLIP modules (eager torch) or the HIP "
+                        "encoders (domain_rag_amd.textenc); tokenizers are host Python either way")
+    p.add_argument("--num_inference_steps", type=int, default=steps)
+    for flag, kw in own:
+        p.add_argument(flag, **kw)
+    p.add_argument("--io_workers", type=int, default=4, help="background PNG encoder processes (0 = write inline like the reference)")
+    p.add_argument("--png", choices=["gpu", "host"], default="gpu",
+                   help=f"{png_files}: 'gpu' = encoded on the device (domain_rag_amd.png: same pixels, not Pillow's bytes), "
+                        f"'host' = Pillow (zlib level 6) in the --io_workers processes{png_note}")
+
+
+def engine_from_args(kind: str, args, device) -> Engine:
+    return Engine(kind, args.model_root, synthetic=args.synthetic_weights, tiny=args.tiny, device=device, text_encoder=args.text_encoder,
+                  linear_precision=args.linear_precision, step_cache=args.step_cache, step_cache_scope=args.step_cache_scope)

@@ -19,9 +19,9 @@ from datetime import datetime
 import torch
 
 from ..engine import Engine, generator_noise, pack_noise
-from ..flux import parse_step_cache
 from .. import hostlogic as H
 from ..retrieval import shard_bounds
+from .engine_args import add_engine_arguments, engine_from_args
 
 COCO_IMAGE_SCALE, TARGET_IMAGE_SCALE, COCO_TEXT_SCALE, TARGET_TEXT_SCALE = 0.8, 1.0, 1.0, 1.0
 PROMPT = ""
@@ -41,29 +41,7 @@ def build_parser():
     p.add_argument("--model_root", type=str, default="./model")
     p.add_argument("--coco_dir", type=str, default="./retrieval/coco/train2017",
                    help="the reference's hard-coded coco_dataset_dir (batch_…:29)")
-    p.add_argument("--synthetic-weights", action="store_true")
-    p.add_argument("--tiny", action="store_true", help="test hook: tiny architectures, small images")
-    p.add_argument("--linear_precision", choices=["bf16", "mxfp8"], default=None,
-                   help="the DiT blocks' Linears: bf16, or OCP MXFP8 operands on the block-scaled matrix instruction (opt-in, lower "
-                        "precision); default: $DRAG_LINEAR_PRECISION, else bf16")
-    p.add_argument("--step_cache", type=parse_step_cache, default=None, metavar="THRESHOLD",
-                   help="first-block step cache of the denoise loop (opt-in, lower fidelity): a step whose first-block residual moved by less "
-                        "than THRESHOLD (relative L1, every image of the batch) since the last computed step reuses that step's remaining "
-                        "blocks; batch neighbours then influence a result (--step_cache_scope image or --ref_batch 1 restores independence); "
-                        "default: $DRAG_STEP_CACHE, else off")
-    p.add_argument("--step_cache_scope", choices=["batch", "image"], default=None,
-                   help="who decides a reuse when --step_cache is on: batch = every image of the batch must be under the threshold; image = "
-                        "every image decides for itself and the remaining blocks run on the others only, so a result does not depend on its "
-                        "batch neighbours; default: $DRAG_STEP_CACHE_SCOPE, else batch")
-    p.add_argument("--text_encoder", choices=["transformers", "hip"], default="transformers",
-                   help="what encodes a prompt without a prompt_cache file: the transformers T5 / CLIP modules (eager torch) or the HIP "
-                        "encoders (domain_rag_amd.textenc); tokenizers are host Python either way")
-    p.add_argument("--num_inference_steps", type=int, default=STEPS)
-    p.add_argument("--size", type=int, default=SIZE)
-    p.add_argument("--io_workers", type=int, default=4, help="background PNG encoder processes (0 = write inline like the reference)")
-    p.add_argument("--png", choices=["gpu", "host"], default="gpu",
-                   help="generated_image_rank{r}.png: 'gpu' = encoded on the device (domain_rag_amd.png: same pixels, not Pillow's bytes), "
-                        "'host' = Pillow (zlib level 6) in the --io_workers processes")
+    add_engine_arguments(p, "--ref_batch", STEPS, "small images", "generated_image_rank{r}.png", own=[("--size", dict(type=int, default=SIZE))])
     p.add_argument("--ref_batch", type=int, default=8, help="references of one target generated per batch (1 = one at a time like the reference)")
     p.add_argument("--fallback-seed", type=int, default=None, help="seed the random-COCO fallback (reference: unseeded)")
     return p
@@ -295,9 +273,7 @@ def main(argv=None):
         results = json.load(f)
     from ..io_pool import ImageWriter
     args.writer = ImageWriter(args.io_workers)
-    engine = Engine("dev", args.model_root, synthetic=args.synthetic_weights, tiny=args.tiny, device=torch.device("cuda", local),
-                    text_encoder=args.text_encoder, linear_precision=args.linear_precision, step_cache=args.step_cache,
-                    step_cache_scope=args.step_cache_scope)
+    engine = engine_from_args("dev", args, torch.device("cuda", local))
     datasets = [args.dataset] if args.dataset else (DATASET_GROUPS[args.dataset_group] if args.dataset_group else list(results))
     tot_ok = tot_bad = 0
     for ds in datasets:

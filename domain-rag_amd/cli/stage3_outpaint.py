@@ -27,8 +27,8 @@ import torch
 
 from .. import hostlogic as H
 from ..engine import Engine, generator_noise, pack_noise
-from ..flux import parse_step_cache
 from ..io_pool import ImageWriter
+from .engine_args import add_engine_arguments, engine_from_args
 
 RESULT_DIR, DATASETS_DIR = "./result", "./datasets"
 
@@ -63,28 +63,7 @@ def build_parser():
     p.add_argument("--model_root", type=str, default="./model")
     p.add_argument("--result_dir", type=str, default=RESULT_DIR)
     p.add_argument("--datasets_dir", type=str, default=DATASETS_DIR)
-    p.add_argument("--synthetic-weights", action="store_true")
-    p.add_argument("--tiny", action="store_true", help="test hook: tiny architectures, min_dimension 64")
-    p.add_argument("--linear_precision", choices=["bf16", "mxfp8"], default=None,
-                   help="the DiT blocks' Linears: bf16, or OCP MXFP8 operands on the block-scaled matrix instruction (opt-in, lower "
-                        "precision); default: $DRAG_LINEAR_PRECISION, else bf16")
-    p.add_argument("--step_cache", type=parse_step_cache, default=None, metavar="THRESHOLD",
-                   help="first-block step cache of the denoise loop (opt-in, lower fidelity): a step whose first-block residual moved by less "
-                        "than THRESHOLD (relative L1, every image of the batch) since the last computed step reuses that step's remaining "
-                        "blocks; batch neighbours then influence a result (--step_cache_scope image or --bg_batch 1 restores independence); "
-                        "default: $DRAG_STEP_CACHE, else off")
-    p.add_argument("--step_cache_scope", choices=["batch", "image"], default=None,
-                   help="who decides a reuse when --step_cache is on: batch = every image of the batch must be under the threshold; image = "
-                        "every image decides for itself and the remaining blocks run on the others only, so a result does not depend on its "
-                        "batch neighbours; default: $DRAG_STEP_CACHE_SCOPE, else batch")
-    p.add_argument("--text_encoder", choices=["transformers", "hip"], default="transformers",
-                   help="what encodes a prompt without a prompt_cache file: the transformers T5 / CLIP modules (eager torch) or the HIP "
-                        "encoders (domain_rag_amd.textenc); tokenizers are host Python either way")
-    p.add_argument("--num_inference_steps", type=int, default=H.NUM_INFERENCE_STEPS)
-    p.add_argument("--io_workers", type=int, default=4, help="background PNG encoder processes (0 = write inline like the reference)")
-    p.add_argument("--png", choices=["gpu", "host"], default="gpu",
-                   help="*_hires_result_* / *_final_result_*: 'gpu' = encoded on the device (domain_rag_amd.png: same pixels, not "
-                        "Pillow's bytes), 'host' = Pillow (zlib level 6) in the --io_workers processes; masks and copies stay with Pillow")
+    add_engine_arguments(p, "--bg_batch", H.NUM_INFERENCE_STEPS, "min_dimension 64", "*_hires_result_* / *_final_result_*", "; masks and copies stay with Pillow")
     p.add_argument("--pictures", choices=["device", "host"], default=PICTURES_DEFAULT,
                    help="device: the generated_image*.png backgrounds are decoded on the device (domain_rag_amd.png.decode_paths; files it "
                         "declines go through Pillow as before) and, with --png gpu, the results are resized back there too; host: Pillow")
@@ -325,9 +304,7 @@ def collect_final_results(process_id, shot, source_process_id=None):
 def run_rank(args, datasets, process_id, rank, world, gpu_process_id=None):
     local = int(os.environ.get("LOCAL_RANK", str(rank))) % max(torch.cuda.device_count(), 1)   # (more ranks than GPUs: share them)
     torch.cuda.set_device(local)
-    engine = Engine("fill", args.model_root, synthetic=args.synthetic_weights, tiny=args.tiny, device=torch.device("cuda", local),
-                    text_encoder=args.text_encoder, linear_precision=args.linear_precision, step_cache=args.step_cache,
-                    step_cache_scope=args.step_cache_scope)
+    engine = engine_from_args("fill", args, torch.device("cuda", local))
     rng = random.Random(None if args.seed is None else args.seed + rank)
     writer = ImageWriter(args.io_workers)
     done, failed = parse_resume_log(args.log_file) if (args.resume or args.failed_only) else (set(), set())

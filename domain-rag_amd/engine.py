@@ -17,12 +17,12 @@ import os
 import numpy as np
 import torch
 
-from . import ops, redux as redux_mod, vae as vae_mod, vit as vit_mod
+from . import redux as redux_mod, vae as vae_mod, vit as vit_mod
+from .denoise import DenoisePipeline
 from .fill_pipeline import FluxFillHIP
-from . import flux as flux_mod
 from .flux import FluxTransformerHIP, latent_image_ids
 from .flux_params import FluxConfig, init_params, load_safetensors_dir
-from .scheduler import flow_sigmas, model_timestep
+from .scheduler import flow_sigmas
 
 TINY = dict(flux=dict(num_layers=1, num_single_layers=1, num_attention_heads=2, joint_attention_dim=256, pooled_projection_dim=64),
             vae=dict(layers_per_block=1), vit=dict(image_size=56, patch_size=14, hidden=192, heads=2, layers=1, intermediate=304),
@@ -160,28 +160,16 @@ class TextCache:
         return self._mem[key]
 
 
-class FluxTxt2ImgHIP:
+class FluxTxt2ImgHIP(DenoisePipeline):
     """``FluxPipeline.__call__(prompt_embeds=…, pooled_prompt_embeds=…, guidance_scale, num_inference_steps, height,
     width, generator)`` of stage 2 (batch_generate_flux_kshot.py:467-474)."""
 
-    def __init__(self, transformer: FluxTransformerHIP, vae: "vae_mod.FluxVaeHIP", use_graph: bool = True, step_cache: float | None = None,
-                 step_cache_scope: str | None = None):
-        self.tr, self.vae, self.dev, self.use_graph = transformer, vae, transformer.device, use_graph
-        # first-block step cache threshold, as FluxFillHIP's: None = $DRAG_STEP_CACHE, else off; 0 = off; on = eager forwards, one cache per call
-        self.step_cache = flux_mod.STEP_CACHE_DEFAULT if step_cache is None else step_cache
-        self.step_cache_scope = flux_mod.STEP_CACHE_SCOPE_DEFAULT if step_cache_scope is None else flux_mod.parse_step_cache_scope(step_cache_scope)
-        self.step_cache_forced = self.step_cache_forced_images = None
-        self.last_step_decisions = self.last_step_reused_images = None
-        self._cache = None
-
     def __call__(self, prompt_embeds, pooled, *, height: int, width: int, guidance_scale: float, num_inference_steps: int,
                  noise_tokens: torch.Tensor, on_step=None) -> torch.Tensor:
-        """``on_step(i, latents)``: called after every Euler update with a bf16 [B, n_tok, 64] COPY of the packed latents
-        (what diffusers hands ``callback_on_step_end`` as ``latents``); used by scripts/accept_real_weights.py"""
         B = prompt_embeds.shape[0]
         h, w = height // 16, width // 16
         key = (B, h, w, prompt_embeds.shape[1])
-        if getattr(self, "_key", None) != key:      # stable addresses: one captured graph serves every call of this shape
+        if self._key != key:      # stable addresses: one captured graph serves every call of this shape
             bf = dict(dtype=torch.bfloat16, device=self.dev)
             self._lat, self._pe, self._pp = torch.empty((B, h * w, 64), **bf), torch.empty_like(prompt_embeds, **bf), torch.empty_like(pooled, **bf)
             self._key = key
@@ -190,20 +178,7 @@ class FluxTxt2ImgHIP:
         sigmas, timesteps = flow_sigmas(num_inference_steps, h * w)
         img_ids, txt_ids = latent_image_ids(h, w), torch.zeros(prompt_embeds.shape[1], 3)
         guidance = torch.full((B,), float(guidance_scale)) if self.tr.cfg.guidance_embeds else None
-        cache = self._cache = flux_mod.pipeline_step_cache(self._cache, self.step_cache, self.step_cache_forced, self.step_cache_scope,
-                                                                 self.step_cache_forced_images)
-        for i in range(num_inference_steps):
-            t = torch.full((B,), model_timestep(timesteps[i]))
-            if cache is not None:
-                v = self.tr.forward(lat, prompt_embeds, pooled, t, img_ids, txt_ids, guidance, cache=cache)
-            else:
-                fwd = self.tr.forward_graphed if self.use_graph else self.tr.forward
-                v = fwd(lat, prompt_embeds, pooled, t, img_ids, txt_ids, guidance)
-            ops.flow_euler_rows(lat, v, B * h * w, 64, 64, 64, float(sigmas[i + 1] - sigmas[i]))
-            if on_step is not None:
-                on_step(i, lat.clone())
-        self.last_step_decisions = None if cache is None else list(cache.decisions)
-        self.last_step_reused_images = None if cache is None else list(cache.reused_images)
+        self.denoise(lat, 64, prompt_embeds, pooled, img_ids, txt_ids, guidance, sigmas, timesteps, 0, num_inference_steps, on_step=on_step)
         return self.vae.decode_tokens(lat, B, h, w, ld=64).clone()      # the decoder's buffer is reused by the next call
 
 
@@ -216,7 +191,7 @@ class Engine:
         """``text_encoder``: what encodes a prompt-cache miss — "transformers" (the reference's modules, eager torch) or "hip"
         (:mod:`.textenc`; with ``synthetic``: seeded encoders and stand-in tokenizers, results kept in memory).
         ``linear_precision``: the DiT blocks' Linears, "bf16" or "mxfp8" (None: $DRAG_LINEAR_PRECISION, else bf16; :mod:`.flux`).
-        ``step_cache``: threshold of the first-block step cache of the denoise loop (:class:`.flux.StepCache`; None: $DRAG_STEP_CACHE, else
+        ``step_cache``: threshold of the first-block step cache of the denoise loop (:class:`.step_cache.StepCache`; None: $DRAG_STEP_CACHE, else
         off; 0: off) — the pipeline's ``step_cache`` attribute; ``step_cache_scope``: who decides a reuse, "batch" (the whole batch) or
         "image" (every image for itself; None: $DRAG_STEP_CACHE_SCOPE, else "batch") — the pipeline's ``step_cache_scope``"""
         assert kind in ("dev", "fill")

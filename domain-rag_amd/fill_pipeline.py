@@ -17,31 +17,14 @@ from __future__ import annotations
 import torch
 
 from . import ops, vae as vae_mod, vit as vit_mod, redux as redux_mod
-from . import flux as flux_mod
+from .denoise import DenoisePipeline
 from .flux import FluxTransformerHIP, latent_image_ids
 from .flux_params import FluxConfig, init_params
-from .scheduler import flow_sigmas, model_timestep, strength_start
+from .scheduler import flow_sigmas, strength_start
 
 
-class FluxFillHIP:
+class FluxFillHIP(DenoisePipeline):
     """Transformer + VAE of FLUX.1-Fill-dev (in_channels 384) with the FluxFillPipeline call sequence."""
-
-    def __init__(self, transformer: FluxTransformerHIP, vae: "vae_mod.FluxVaeHIP", use_graph: bool = True, step_cache: float | None = None,
-                 step_cache_scope: str | None = None):
-        self.tr, self.vae = transformer, vae
-        self.dev = transformer.device
-        self.use_graph = use_graph      # replay the DiT forward as a hipGraph (bit-identical outputs; frees the host thread)
-        # first-block step cache threshold (flux.StepCache; opt-in): None = $DRAG_STEP_CACHE, else off; 0 = off.  When on, every step runs
-        # the eager forward with one cache that is reset at the start of each call, and use_graph is ignored
-        self.step_cache = flux_mod.STEP_CACHE_DEFAULT if step_cache is None else step_cache
-        # who decides a reuse, "batch" or "image" (flux.StepCache's ``scope``): None = $DRAG_STEP_CACHE_SCOPE, else "batch"
-        self.step_cache_scope = flux_mod.STEP_CACHE_SCOPE_DEFAULT if step_cache_scope is None else flux_mod.parse_step_cache_scope(step_cache_scope)
-        self.step_cache_forced = None   # measurement only (scripts/bench_step_cache.py): StepCache's ``forced`` pattern
-        self.step_cache_forced_images = None      # ... and its ``forced_images`` (scope "image")
-        self.last_step_decisions = None
-        self.last_step_reused_images = None       # per step, the per-image ``reused`` (StepCache.reused_images)
-        self._cache = None
-        self._key = None
 
     def _buffers(self, B, H, W, St):
         key = (B, H, W, St)
@@ -80,22 +63,7 @@ class FluxFillHIP:
             t0 = strength_start(num_inference_steps, strength)
             ops.scale_noise_rows(hv, noise_tokens, B * Si, 64, C, 64, float(sigmas[t0]))
             guidance = torch.full((B,), float(guidance_scale))
-            cache = self._cache = flux_mod.pipeline_step_cache(self._cache, self.step_cache, self.step_cache_forced, self.step_cache_scope,
-                                                                     self.step_cache_forced_images)
-            for i in range(t0, num_inference_steps):
-                t = torch.full((B,), model_timestep(timesteps[i]))
-                timed = recorder is not None and (i - t0) % recorder.every == 0
-                ops.set_recorder(recorder if timed else None)
-                if cache is not None:
-                    v = self.tr.forward(hidden, prompt_embeds, pooled, t, self._img_ids, self._txt_ids, guidance, cache=cache)
-                else:
-                    fwd = self.tr.forward_graphed if (self.use_graph and not timed) else self.tr.forward
-                    v = fwd(hidden, prompt_embeds, pooled, t, self._img_ids, self._txt_ids, guidance)
-                ops.flow_euler_rows(hv, v, B * Si, 64, C, 64, float(sigmas[i + 1] - sigmas[i]))
-                if on_step is not None:       # diffusers' callback_on_step_end sees the packed latents after the update
-                    on_step(i, hidden[:, :, :64].clone())
-            self.last_step_decisions = None if cache is None else list(cache.decisions)
-            self.last_step_reused_images = None if cache is None else list(cache.reused_images)
+            self.denoise(hidden, C, prompt_embeds, pooled, self._img_ids, self._txt_ids, guidance, sigmas, timesteps, t0, num_inference_steps, recorder, on_step)
             ops.set_recorder(recorder)
             return self.vae.decode_tokens(hv, B, h, w, ld=C).clone()      # the decoder's buffer is reused by the next call
         finally:

@@ -18,14 +18,14 @@ only owns the device buffers.  MI355X-first layout decisions:
 from __future__ import annotations
 
 import math
-from typing import NamedTuple, Sequence
+import os
 
 import torch
 
-import os
-
 from . import ops
 from .flux_params import FluxConfig
+from .step_cache import (STEP_CACHE_DEFAULT, STEP_CACHE_SCOPE_DEFAULT, STEP_CACHE_SCOPES, StepCache, StepDecision, compact_pairs,      # noqa: F401
+                         parse_step_cache, parse_step_cache_scope, pipeline_step_cache)
 
 _SEPARATE_QPREP = os.environ.get("DRAG_QPREP_SEPARATE", "") not in ("", "0")     # measurement switches, read once
 # single blocks: to_q|k|v + proj_mlp as ONE two-destination launch.  At the headline's 42 696 rows it saves a partial tile round
@@ -46,176 +46,6 @@ if _LINEAR_PRECISION not in LINEAR_PRECISIONS:
 # the bf16 GEMM) every headline shape measured (MX + quantise) / bf16 between 1.62 and 1.84, so all six stay; the single blocks' 21 504-row
 # weight runs as its 9216- and 12 288-row ranges on the MX route, both listed.
 _MX_STAYS_BF16: frozenset = frozenset({(9216, 3072), (3072, 3072), (12288, 3072), (3072, 12288), (21504, 3072), (3072, 15360)})
-
-
-def parse_step_cache(text: str | None) -> float | None:
-    """a step-cache threshold as the environment / a command line gives it: None, "" and 0 mean off (None); a negative, NaN or unparsable
-    value raises ValueError; ``inf`` is a threshold (every step whose ratio is finite reuses)"""
-    if text is None or str(text).strip() == "":
-        return None
-    try:
-        v = float(text)
-    except (TypeError, ValueError):
-        raise ValueError(f"step cache threshold must be a number >= 0, not {text!r}") from None
-    if math.isnan(v) or v < 0:
-        raise ValueError(f"step cache threshold must be a number >= 0, not {text!r}")
-    return v if v > 0 else None
-
-
-# the first-block step cache (StepCache below; opt-in, no default threshold): $DRAG_STEP_CACHE=<threshold> sets the process default of the
-# pipelines' ``step_cache``, read once; unset, empty or 0 = off
-STEP_CACHE_DEFAULT = parse_step_cache(os.environ.get("DRAG_STEP_CACHE", ""))
-
-
-STEP_CACHE_SCOPES = ("batch", "image")
-
-
-def parse_step_cache_scope(text: str | None) -> str:
-    """a step-cache scope as the environment / a command line gives it: None and "" mean "batch"; anything but "batch" / "image" raises"""
-    if text is None or str(text).strip() == "":
-        return "batch"
-    scope = str(text).strip()
-    if scope not in STEP_CACHE_SCOPES:
-        raise ValueError(f"step cache scope must be one of {STEP_CACHE_SCOPES}, not {text!r}")
-    return scope
-
-
-# who decides a reuse: "batch" (the batch as a whole: every image under the threshold) or "image" (every image for itself; the remaining
-# blocks run on the computing images only); $DRAG_STEP_CACHE_SCOPE sets the process default of the pipelines' ``step_cache_scope``, read once
-STEP_CACHE_SCOPE_DEFAULT = parse_step_cache_scope(os.environ.get("DRAG_STEP_CACHE_SCOPE", ""))
-
-
-class StepDecision(NamedTuple):
-    """one forward's entry of ``StepCache.decisions``: the per-image first-block residual ratios against the last computed step (None when
-    there was none to compare with) and whether the step reused that step's cached residual (scope "image": whether EVERY image did;
-    ``StepCache.reused_images`` has the per-image answer)"""
-    ratios: tuple | None
-    reused: bool
-
-
-def compact_pairs(reused: Sequence[bool]) -> tuple:
-    """``(k, pairs)`` that bring the computing images of a batch to its front: ``k`` is the number of computing (not reused) images, and
-    ``pairs`` exchange each reusing image that sits in a slot < k with a computing image that sits in a slot >= k, both taken in increasing
-    order (there are equally many of each).  After the swaps slots 0 ... k-1 hold exactly the computing images; the same swaps again
-    restore the order; a batch that is already compact gives no pairs."""
-    reused = [bool(r) for r in reused]
-    k = reused.count(False)
-    front = [i for i in range(k) if reused[i]]
-    back = [i for i in range(k, len(reused)) if not reused[i]]
-    return k, list(zip(front, back))
-
-
-class StepCache:
-    """First-block cache of the DiT forward (``FluxTransformerHIP.forward(..., cache=...)``): after double block 0 the change of that block's
-    residual since the last COMPUTED step, sum |new - old| / sum |old| per image, is compared with ``threshold``.  The comparison is always
-    against the last computed step, so the drift is bounded by the threshold and not by the number of reuses.  A NaN or infinite ratio
-    never reuses.
-
-    ``scope``: "batch" (default) — when every image of the batch is under the threshold, the cached residual of the remaining blocks is
-    added instead of running them; one image over it makes all compute.  "image" — every image decides for itself: the remaining blocks run
-    at batch k on the k computing images, compacted to the front of the workspace, and each reusing image adds its own cached residual, so
-    an image's result does not depend on its batch neighbours.  "last computed step" is then per image.
-
-    ``forced``: for measurement and tests — ``forced[i]`` is the value ``reused`` takes in forward number ``i`` since ``reset()`` whatever
-    the ratios say (a forward with nothing valid to reuse still computes); forwards beyond its length follow the threshold.
-    ``forced_images`` (scope "image" only): the same per image — ``forced_images[i]`` is a sequence of B bools for forward ``i``.
-
-    ``decisions`` holds one :class:`StepDecision` per forward, ``reused_images`` the per-image tuple of bools next to it (under "batch"
-    all equal).
-
-    State: three dense bf16 [B, Si, D] buffers — E (scratch: the current first-block residual), F (the first-block residual of the last
-    computed step), R (the residual of that step's remaining blocks, image rows only: the final projection reads nothing else) — the float64
-    ratios and the reduction workspace.  Validity is per image (``valid_images``; ``valid``: all of them): every image is invalid after
-    ``reset()``, after a change of (B, Si, D) and after a change of the model's ``linear_precision``.  Reading the ratios back is the one
-    host synchronisation per step."""
-
-    def __init__(self, threshold: float, forced: Sequence[bool] | None = None, scope: str = "batch",
-                 forced_images: Sequence[Sequence[bool]] | None = None):
-        self._key = self._precision = None
-        self.configure(threshold, forced, scope, forced_images)
-        self.E = self.F = self.R = self.ratios = self.workspace = None
-        self.reset()
-
-    def configure(self, threshold: float, forced: Sequence[bool] | None = None, scope: str = "batch",
-                  forced_images: Sequence[Sequence[bool]] | None = None) -> None:
-        threshold = float(threshold)
-        if math.isnan(threshold) or threshold < 0:
-            raise ValueError(f"StepCache threshold must be >= 0, not {threshold!r}")
-        if scope not in STEP_CACHE_SCOPES:
-            raise ValueError(f"StepCache scope must be one of {STEP_CACHE_SCOPES}, not {scope!r}")
-        if forced_images is not None and scope != "image":
-            raise ValueError('StepCache forced_images needs scope="image" (forced is the whole-batch form)')
-        self.threshold = threshold
-        self.scope = scope
-        self.forced = None if forced is None else [bool(v) for v in forced]
-        self.forced_images = None if forced_images is None else [tuple(bool(v) for v in m) for m in forced_images]
-
-    @property
-    def valid(self) -> bool:
-        return bool(self.valid_images) and all(self.valid_images)
-
-    @valid.setter
-    def valid(self, value: bool) -> None:
-        self.valid_images = [bool(value)] * (self._key[0] if self._key else 0)
-
-    def reset(self) -> None:
-        self.valid = False
-        self.decisions: list[StepDecision] = []
-        self.reused_images: list[tuple] = []
-
-    def _prepare(self, B: int, Si: int, D: int, precision: str, device) -> None:
-        key = (B, Si, D, str(device))
-        if self._key != key:
-            bf = dict(dtype=torch.bfloat16, device=device)
-            self.E, self.F, self.R = (torch.empty((B, Si, D), **bf) for _ in range(3))
-            self.ratios = torch.empty(B, dtype=torch.float64, device=device)
-            self.workspace = torch.empty(ops.stepcache_workspace_bytes(B, Si, D), dtype=torch.uint8, device=device)
-            self._key, self.valid = key, False
-        if self._precision != precision:
-            self._precision, self.valid = precision, False
-        if len(self.valid_images) != B:          # reset() before the first forward did not know B
-            self.valid = False
-
-    def _decide(self) -> tuple:
-        """after ``stepcache_delta``: read the ratios back, record the decision, return the per-image ``reused``"""
-        valid = self.valid_images
-        B, n = len(valid), len(self.decisions)
-        ratios = None
-        if any(valid):
-            ratios = tuple(r if v else None for r, v in zip(self.ratios.cpu().tolist(), valid))
-        if self.scope == "image":
-            if self.forced_images is not None and n < len(self.forced_images):
-                want = self.forced_images[n]
-                if len(want) != B:
-                    raise ValueError(f"StepCache forced_images[{n}] has {len(want)} entries for a batch of {B}")
-            elif self.forced is not None and n < len(self.forced):
-                want = (self.forced[n],) * B
-            else:
-                want = tuple(v and ratios[b] < self.threshold for b, v in enumerate(valid))      # NaN and +inf compare False
-            mask = tuple(bool(v and w) for v, w in zip(valid, want))
-        else:
-            if self.forced is not None and n < len(self.forced):
-                want = self.forced[n]
-            else:
-                want = self.valid and all(r < self.threshold for r in ratios)      # NaN and +inf compare False
-            mask = (bool(self.valid and want),) * B
-        self.decisions.append(StepDecision(ratios, all(mask)))
-        self.reused_images.append(mask)
-        return mask
-
-
-def pipeline_step_cache(cache: StepCache | None, threshold: float | None, forced: Sequence[bool] | None = None, scope: str = "batch",
-                        forced_images: Sequence[Sequence[bool]] | None = None) -> StepCache | None:
-    """the cache one pipeline call runs with: None when the mode is off (``threshold`` None or 0); else the pipeline's one StepCache (its
-    buffers are kept from call to call), brought to ``threshold`` / ``forced`` / ``scope`` / ``forced_images`` and RESET, so that no state
-    leaks between samples"""
-    if threshold is None or float(threshold) == 0:
-        return None
-    if cache is None:
-        return StepCache(threshold, forced, scope, forced_images)
-    cache.configure(threshold, forced, scope, forced_images)
-    cache.reset()
-    return cache
 
 
 def rope_tables(ids: torch.Tensor, axes_dims=(16, 56, 56), theta: float = 10000.0):
@@ -544,10 +374,8 @@ class FluxTransformerHIP:
                 cache: StepCache | None = None):
         """hidden bf16 [B, S_img, in]; enc bf16 [B, S_txt, J]; pooled bf16 [B, P]; timestep / guidance
         fp32 [B] host or device; returns bf16 [B, S_img, out] (a view of an internal workspace).
-        ``cache``: a :class:`StepCache` (opt-in; None is the plain forward, the same launches in the same order): the first double block
-        runs, then the step either reuses the cached residual of the remaining blocks or computes them and refreshes the cache.  Under
-        the cache's scope "image" a step on which only some images reuse runs the remaining blocks at the batch size of the others, on the
-        same workspace with those images swapped to its front; a step on which all or none reuse launches what scope "batch" launches."""
+        ``cache``: a :class:`StepCache` (opt-in; None is the plain forward, the same launches in the same order): after the first double block the
+        step (scope "image": each image) reuses the cached residual of the remaining blocks, or computes them and refreshes the cache."""
         cfg = self.cfg
         if cache is not None and (cfg.num_layers < 1 or cfg.num_layers + cfg.num_single_layers < 2):
             raise ValueError("a step cache needs a double block and at least one further block")
@@ -587,57 +415,17 @@ class FluxTransformerHIP:
             taps["x_embed"] = x[:, St:].clone(); taps["ctx_embed"] = x[:, :St].clone()
 
         nrm_img = nrm.view(-1)[: Mi * D]
-        nb, computing, pairs = B, None, ()      # the batch blocks 1... run at; scope "image", mixed step: the computing images, the compaction
+        nb = B      # the batch size blocks 1... run at: under a step cache 0 on a reused step, the number of computing images on a mixed one
         if self.double:
-            if cache is not None:      # step cache, hook 1: the image rows as block 0 receives them
-                cache._prepare(B, Si, D, self._linear_precision, self.device)
-                cache.E.copy_(x[:, St:])
+            if cache is not None:
+                cache.before_first_block(x, B, St, Si, D, self._linear_precision, self.device)
             self._double_block(ws, 0, B, St, Si, cos, sin, taps)
             if cache is not None:
-                # step cache, hook 2: E <- block 0's residual of the image rows, its ratio against the last computed step's (F), the decision
-                ops.stepcache_delta(x_img, cache.E, cache.F if any(cache.valid_images) else None, cache.ratios, cache.workspace, B, Si, D, S * D)
-                if taps is not None:
-                    taps["cache.delta"] = cache.E.clone()
-                mask = cache._decide()
-                if all(mask):      # add that step's residual of the remaining blocks and go to the final LayerNorm; F and R stay
-                    ops.stepcache_apply(x_img, cache.R, B, Si, D, S * D, +1)
-                    if taps is not None:
-                        taps["cache.x_img"] = x[:, St:].clone()
-                    nb = 0
-                elif not any(mask):
-                    # hook 3, computed step: this residual becomes F; R <- the image rows now, turned into the residual after the last block
-                    cache.E, cache.F = cache.F, cache.E
-                    cache.valid = False
-                    cache.R.copy_(x[:, St:])
-                else:
-                    # scope "image", some images reuse: hook 3 for the computing images, the reuse for the others, then the computing
-                    # images go to the front of the batch (whole joint rows and their modulation rows)
-                    computing = [b for b in range(B) if not mask[b]]
-                    ops.stepcache_copy_images(cache.F, cache.E, Si * D, B, Si, D, computing)
-                    ops.stepcache_copy_images(cache.R, x_img, S * D, B, Si, D, computing)
-                    ops.stepcache_apply_images(x_img, cache.R, B, Si, D, S * D, +1, [b for b in range(B) if mask[b]])
-                    for b in computing:
-                        cache.valid_images[b] = False
-                    nb, pairs = compact_pairs(mask)
-                    ops.stepcache_swap(x, B, S, D, S * D, pairs)
-                    ops.stepcache_swap(mod, B, 1, LM, LM, pairs)
-                    if taps is not None:
-                        slots = list(range(B))
-                        for a, b in pairs:
-                            slots[a], slots[b] = slots[b], slots[a]
-                        taps["cache.slots"] = tuple(slots)      # the image each slot holds while blocks 1... run
+                nb = cache.after_first_block(x, mod, B, St, Si, D, taps)
         if nb:
             self._blocks_after_first(ws, nb, St, Si, cos, sin, taps)
-        if computing is not None:
-            # the tail runs at batch B in the batch's own order: it reads the image rows and norm_out's modulation, not the text rows
-            ops.stepcache_swap(x_img, B, Si, D, S * D, pairs)
-            ops.stepcache_swap(mod, B, 1, LM, LM, pairs)
-            ops.stepcache_apply_images(x_img, cache.R, B, Si, D, S * D, -1, computing)      # capture, per image
-            for b in computing:
-                cache.valid_images[b] = True
-        elif cache is not None and nb:
-            ops.stepcache_apply(x_img, cache.R, B, Si, D, S * D, -1)      # capture: R <- x_img - (x_img after block 0)
-            cache.valid = True
+        if cache is not None:
+            cache.after_last_block(x, mod, B, St, Si, D)
         mo = self.mod_off["out"]             # AdaLayerNormContinuous: scale, shift
         ops.layernorm(x_img, nrm_img, Mi, D, scale=modv[mo:], shift=modv[mo + D:], ldx=D, rows_per_batch=Si,
                       x_batch_stride=S * D, ld_mod=LM)
@@ -665,11 +453,11 @@ class FluxTransformerHIP:
         rope_key = self._ids_key(txt_ids, img_ids)
         key = (hidden.data_ptr(), enc.data_ptr(), pooled.data_ptr(), tuple(hidden.shape), tuple(enc.shape), tuple(pooled.shape),
                guidance is None, rope_key, self._linear_precision)
-        cache = self.__dict__.setdefault("_graphs", {})
-        ent = cache.pop(key, None)
+        graphs = self.__dict__.setdefault("_graphs", {})
+        ent = graphs.pop(key, None)
         if ent is None:
-            while len(cache) >= self.MAX_GRAPHS:
-                cache.pop(next(iter(cache)))                 # least recently used: drops its graph, workspace and tables
+            while len(graphs) >= self.MAX_GRAPHS:
+                graphs.pop(next(iter(graphs)))                 # least recently used: drops its graph, workspace and tables
             # private buffers for this capture: nothing the eager path (or another graph) will ever reallocate
             self._ws_key = self._rope_key = None
             self._t1000 = self._g1000 = None
@@ -685,7 +473,7 @@ class FluxTransformerHIP:
             # hand the buffers over: the next eager forward / capture allocates its own
             self._ws_key = self._rope_key = None
             self._t1000 = self._g1000 = None
-        cache[key] = ent                                     # (re)insert as most recently used
+        graphs[key] = ent                                     # (re)insert as most recently used
         t1000, g1000 = ent["times"]
         t1000.copy_((t.to(torch.bfloat16) * 1000).float())
         if g is not None:

@@ -265,7 +265,7 @@ def _hip_pipes(args, kind, encoders):
                                                           tokenizer=tok, tokenizer_2=tok2).to("cuda")
     cls = compat.FluxFillPipeline if kind == "fill" else compat.FluxPipeline
     pipe = cls.from_pretrained(flux).to("cuda")
-    if getattr(args, "step_cache", None):       # --step-cache: the HIP side runs with the first-block step cache (flux.StepCache)
+    if getattr(args, "step_cache", None):       # --step-cache: the HIP side runs with the first-block step cache (step_cache.StepCache)
         pipe.pipe.step_cache = args.step_cache
         pipe.pipe.step_cache_scope = getattr(args, "step_cache_scope", None) or "batch"
     return prior, pipe

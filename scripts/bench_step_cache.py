@@ -1,4 +1,4 @@
-"""What the first-block step cache (flux.StepCache) costs and saves on the headline workload: SyntheticFillJob (B = 8, 1024^2, 30 Flux-Fill
+"""What the first-block step cache (step_cache.StepCache) costs and saves on the headline workload: SyntheticFillJob (B = 8, 1024^2, 30 Flux-Fill
 steps), one process, the passes interleaved round by round:
 
   off                the product's default path (hipGraph replay, no cache)

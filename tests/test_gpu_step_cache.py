@@ -1,4 +1,4 @@
-"""The first-block step cache of the Flux DiT (``flux.StepCache``, ``FluxTransformerHIP.forward(..., cache=...)``) and its pipeline switch.
+"""The first-block step cache of the Flux DiT (``step_cache.StepCache``, ``FluxTransformerHIP.forward(..., cache=...)``) and its pipeline switch.
 
 What is pinned, and from what:
   * off is untouched: ``cache=None`` and a cache that never fires give equal bits and equal recorded launch sequences;

@@ -1,4 +1,4 @@
-"""The step cache's scope "image" (``flux.StepCache(scope="image")``): every image of a batch decides for itself, and a step on which only
+"""The step cache's scope "image" (``step_cache.StepCache(scope="image")``): every image of a batch decides for itself, and a step on which only
 some reuse runs the remaining blocks at the batch size of the others, on the same workspace with those images swapped to its front.
 
 What is pinned, all of it bit for bit (nothing here has a tolerance: the per-image arithmetic of the forward does not depend on the batch

@@ -1,4 +1,4 @@
-"""Host side of the step cache's scope (``flux.StepCache(scope=...)``): the compaction helper, the scope's parsing, the refusal of
+"""Host side of the step cache's scope (``step_cache.StepCache(scope=...)``): the compaction helper, the scope's parsing, the refusal of
 ``forced_images`` under "batch", the unchanged ``StepDecision`` and the two output writers' additions (no GPU)."""
 import itertools
 import os
