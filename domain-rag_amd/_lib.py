@@ -89,6 +89,7 @@ SIGNATURES = {
     "drag_stepcache_swap_bf16": (c_int, [c_void_p] + [c_int] * 3 + [c_int64, c_void_p, c_int, c_void_p]),
     "drag_stepcache_apply_images_bf16": (c_int, [c_void_p, c_void_p] + [c_int] * 3 + [c_int64, c_int, c_void_p, c_int, c_void_p]),
     "drag_stepcache_copy_images_bf16": (c_int, [c_void_p, c_void_p, c_int64] + [c_int] * 3 + [c_void_p, c_int, c_void_p]),
+    "drag_stepcache_forecast_images_bf16": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_int64, c_void_p, c_void_p, c_int, c_void_p]),
     "drag_act_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "drag_timestep_embedding_bf16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "drag_flow_euler_step_bf16": (c_int, [c_void_p, c_void_p, c_float, c_int64, c_void_p]),

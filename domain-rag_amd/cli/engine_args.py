@@ -2,7 +2,7 @@
 from __future__ import annotations
 
 from ..engine import Engine
-from ..step_cache import parse_step_cache
+from ..step_cache import parse_step_cache, parse_step_cache_count, parse_step_cache_order
 
 
 def add_engine_arguments(p, batch_flag: str, steps: int, tiny: str, png_files: str, png_note: str = "", own=()) -> None:
@@ -22,6 +22,14 @@ def add_engine_arguments(p, batch_flag: str, steps: int, tiny: str, png_files: s
                    help="who decides a reuse when --step_cache is on: batch = every image of the batch must be under the threshold; image = "
                         "every image decides for itself and the remaining blocks run on the others only, so a result does not depend on its "
                         "batch neighbours; default: $DRAG_STEP_CACHE_SCOPE, else batch")
+    p.add_argument("--step_cache_order", type=parse_step_cache_order, default=None, metavar="0|1",
+                   help="what a reused step adds when --step_cache is on: 0 = the cached residual of the last computed step as it is; 1 = its "
+                        "first-order forecast along the timestep, from the last two computed steps; default: $DRAG_STEP_CACHE_ORDER, else 0")
+    p.add_argument("--step_cache_max_run", type=lambda v: parse_step_cache_count(v, "max_run"), default=None, metavar="N",
+                   help="when --step_cache is on: after N reused steps in a row the next one computes (per image under --step_cache_scope "
+                        "image); 0 = no limit; default: $DRAG_STEP_CACHE_MAX_RUN, else 0")
+    p.add_argument("--step_cache_warmup", type=lambda v: parse_step_cache_count(v, "warmup"), default=None, metavar="N",
+                   help="when --step_cache is on: the first N steps of a denoise loop compute; default: $DRAG_STEP_CACHE_WARMUP, else 0")
     p.add_argument("--text_encoder", choices=["transformers", "hip"], default="transformers",
                    help="what encodes a prompt without a prompt_cache file: the transformers T5 / CLIP modules (eager torch) or the HIP "
                         "encoders (domain_rag_amd.textenc); tokenizers are host Python either way")
@@ -34,6 +42,13 @@ def add_engine_arguments(p, batch_flag: str, steps: int, tiny: str, png_files: s
                         f"'host' = Pillow (zlib level 6) in the --io_workers processes{png_note}")
 
 
+def pipe_step_cache_switches(pipe) -> tuple:
+    """(threshold, scope, order, max_run, warmup) of a pipeline, for the stages' two parameter writers"""
+    return (getattr(pipe, "step_cache", None), getattr(pipe, "step_cache_scope", "batch"), getattr(pipe, "step_cache_order", 0),
+            getattr(pipe, "step_cache_max_run", 0), getattr(pipe, "step_cache_warmup", 0))
+
+
 def engine_from_args(kind: str, args, device) -> Engine:
     return Engine(kind, args.model_root, synthetic=args.synthetic_weights, tiny=args.tiny, device=device, text_encoder=args.text_encoder,
-                  linear_precision=args.linear_precision, step_cache=args.step_cache, step_cache_scope=args.step_cache_scope)
+                  linear_precision=args.linear_precision, step_cache=args.step_cache, step_cache_scope=args.step_cache_scope,
+                  step_cache_order=args.step_cache_order, step_cache_max_run=args.step_cache_max_run, step_cache_warmup=args.step_cache_warmup)

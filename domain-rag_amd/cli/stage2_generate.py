@@ -21,7 +21,7 @@ import torch
 from ..engine import Engine, generator_noise, pack_noise
 from .. import hostlogic as H
 from ..retrieval import shard_bounds
-from .engine_args import add_engine_arguments, engine_from_args
+from .engine_args import add_engine_arguments, engine_from_args, pipe_step_cache_switches
 
 COCO_IMAGE_SCALE, TARGET_IMAGE_SCALE, COCO_TEXT_SCALE, TARGET_TEXT_SCALE = 0.8, 1.0, 1.0, 1.0
 PROMPT = ""
@@ -51,12 +51,13 @@ DATASET_GROUPS = {"dataset1": ["ArTaxOr", "clipart1k"], "dataset2": ["DIOR", "FI
                   "dataset4": ["NWPU_VHR_10", "Camouflage"]}
 
 
-def params_txt_step_cache(step_cache, scope: str = "batch") -> str:
-    """the line params.txt gains when the step cache is on, and one more when its scope is "image"; nothing when it is off (the file is then
-    byte-identical to the reference's)"""
+def params_txt_step_cache(step_cache, scope: str = "batch", order: int = 0, max_run: int = 0, warmup: int = 0) -> str:
+    """the line params.txt gains when the step cache is on, and one more each when its scope is "image", its order 1, a reuse limit > 0;
+    nothing when it is off (the file is then byte-identical to the reference's)"""
     if not step_cache:
         return ""
-    return f"步骤缓存阈值: {step_cache}\n" + (f"步骤缓存范围: {scope}\n" if scope == "image" else "")
+    return (f"步骤缓存阈值: {step_cache}\n" + (f"步骤缓存范围: {scope}\n" if scope == "image" else "") + (f"步骤缓存阶数: {order}\n" if order == 1 else "")
+            + (f"步骤缓存最大连续复用: {max_run}\n" if max_run > 0 else "") + (f"步骤缓存预热步数: {warmup}\n" if warmup > 0 else ""))
 
 
 def generate_ranked(engine: Engine, target_path, items, sdir, args, database):
@@ -116,7 +117,7 @@ def generate_ranked(engine: Engine, target_path, items, sdir, args, database):
                         f.write(f"数据库类型: {database}\n参考图像权重: {COCO_IMAGE_SCALE}\n目标图像权重: {TARGET_IMAGE_SCALE}\n"
                                 f"参考文本权重: {COCO_TEXT_SCALE}\n目标文本权重: {TARGET_TEXT_SCALE}\n提示词: {PROMPT}\n指导比例: {GUIDANCE}\n"
                                 f"推理步数: {args.num_inference_steps}\n生成图像尺寸: {w}x{h}\n原始图像尺寸: {tgt_img.size[0]}x{tgt_img.size[1]}\n"
-                                + params_txt_step_cache(getattr(engine.pipe, "step_cache", None), getattr(engine.pipe, "step_cache_scope", "batch")))
+                                + params_txt_step_cache(*pipe_step_cache_switches(engine.pipe)))
                 rs = f"rank{rank}" if rank is not None else ""
                 ss = f"_sim{similarity:.4f}" if similarity is not None else ""
                 with open(os.path.join(sdir, f"ref_info{rs}{ss}.txt"), "w") as f:

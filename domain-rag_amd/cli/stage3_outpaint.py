@@ -28,7 +28,7 @@ import torch
 from .. import hostlogic as H
 from ..engine import Engine, generator_noise, pack_noise
 from ..io_pool import ImageWriter
-from .engine_args import add_engine_arguments, engine_from_args
+from .engine_args import add_engine_arguments, engine_from_args, pipe_step_cache_switches
 
 RESULT_DIR, DATASETS_DIR = "./result", "./datasets"
 
@@ -71,12 +71,13 @@ def build_parser():
     return p
 
 
-def step_cache_params(step_cache, scope: str = "batch") -> dict:
-    """what a result's parameter JSON gains when the step cache is on (and ``step_cache_scope`` when that is "image"); nothing when it is off
-    (the file is then byte-identical)"""
+def step_cache_params(step_cache, scope: str = "batch", order: int = 0, max_run: int = 0, warmup: int = 0) -> dict:
+    """what a result's parameter JSON gains when the step cache is on (and ``step_cache_scope`` when that is "image", ``step_cache_order``
+    when it is 1, the two reuse limits when they are > 0); nothing when it is off (the file is then byte-identical)"""
     if not step_cache:
         return {}
-    return {"step_cache": step_cache, **({"step_cache_scope": scope} if scope == "image" else {})}
+    return {"step_cache": step_cache, **({"step_cache_scope": scope} if scope == "image" else {}), **({"step_cache_order": order} if order == 1 else {}),
+            **({"step_cache_max_run": max_run} if max_run > 0 else {}), **({"step_cache_warmup": warmup} if warmup > 0 else {})}
 
 
 def dataset_result_dirs(result_dir, dataset, shot):
@@ -260,7 +261,7 @@ def process_sample(engine: Engine, args, dataset, sample_id, sample_dir, shot, p
                           "min_dimension_used": min_dim, "up_scale_factor": up, "down_scale_factor": down, "was_upscaled": wu,
                           "was_downscaled": wd, "bbox_coords_list": bboxes, "processed_bbox_coords_list": pb,
                           "image_id": info["id"] if info.get("id") is not None else "unknown", "num_bbox": len(bboxes)}
-                params.update(step_cache_params(getattr(engine.pipe, "step_cache", None), getattr(engine.pipe, "step_cache_scope", "batch")))
+                params.update(step_cache_params(*pipe_step_cache_switches(engine.pipe)))
                 params_path = os.path.join(out_dir, f"{prefix}_params{suffix}.json")
                 with open(params_path, "w") as f:
                     json.dump(params, f, indent=2)

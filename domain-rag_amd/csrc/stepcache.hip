@@ -2,7 +2,7 @@
 //
 // All address image rows as drag_layernorm_modulate_bf16 does: `rows_per_batch` rows of `cols` bf16 elements, row stride `cols`, batch
 // stride `x_batch_stride` — an image's rows are one contiguous run of rows_per_batch * cols elements inside the joint [B, S, D] buffer,
-// behind its text rows.  The dense operands (e, f, r) are [B, rows_per_batch, cols].
+// behind its text rows.  The dense operands (e, f, r, p) are [B, rows_per_batch, cols].
 //
 // Memory-bound streaming kernels: 16-byte loads and stores (8 bf16 per lane), a grid capped at 2048 workgroups of 256 threads with the rest
 // grid-strided.  The residual ratio is summed in float64 from the first term on (bf16 -> float64 is exact, so only the order of summation
@@ -150,6 +150,44 @@ __global__ __launch_bounds__(SC_THREADS) void stepcache_apply_images_kernel(bf16
                                                                             long long x_bs, ScList images) {
   const int b = images.v[blockIdx.y];
   sc_apply_image<ADD>(x + (long long)b * x_bs, r + (long long)b * n8 * 8, n8);
+}
+
+// the coefficients of a forecast's listed images, next to their indices in the argument struct (validated on the host: all finite)
+struct ScCoef {
+  float v[SC_MAX_LIST];
+};
+
+// one element of the first-order forecast: x + (c * (r - p) + r), four individually rounded float32 operations.  Contraction is off for
+// the block: c * d + r must not become an FMA (the reference arithmetic is numpy float32, which cannot fuse)
+__device__ __forceinline__ float sc_forecast(float x, float r, float p, float c) {
+#pragma clang fp contract(off)
+  const float d = r - p;
+  const float m = c * d;
+  const float f = m + r;
+  return x + f;
+}
+
+// x[b] <- bf16(f32(x) + (c * (f32(r) - f32(p)) + f32(r))) for the listed images b = images.v[i], c = coef.v[i]; r and p stay indexed by image
+__global__ __launch_bounds__(SC_THREADS) void stepcache_forecast_images_kernel(bf16_t* __restrict__ x, const bf16_t* __restrict__ r,
+                                                                              const bf16_t* __restrict__ p, long long n8, long long x_bs,
+                                                                              ScList images, ScCoef coef) {
+  const int b = images.v[blockIdx.y];
+  const float c = coef.v[blockIdx.y];
+  bf16_t* xb = x + (long long)b * x_bs;
+  const bf16_t* rb = r + (long long)b * n8 * 8;
+  const bf16_t* pb = p + (long long)b * n8 * 8;
+  const long long stride = (long long)gridDim.x * SC_THREADS;
+  for (long long i = (long long)blockIdx.x * SC_THREADS + threadIdx.x; i < n8; i += stride) {
+    const u32x4_t xr = *(const u32x4_t*)(xb + i * 8);
+    const u32x4_t rr = *(const u32x4_t*)(rb + i * 8);
+    const u32x4_t pr = *(const u32x4_t*)(pb + i * 8);
+    u32x4_t o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      o[j] = pack2bf(sc_forecast(bf2f((bf16_t)(xr[j] & 0xffff)), bf2f((bf16_t)(rr[j] & 0xffff)), bf2f((bf16_t)(pr[j] & 0xffff)), c),
+                     sc_forecast(bf2f((bf16_t)(xr[j] >> 16)), bf2f((bf16_t)(rr[j] >> 16)), bf2f((bf16_t)(pr[j] >> 16)), c));
+    *(u32x4_t*)(xb + i * 8) = o;
+  }
 }
 
 // dst[b] <- src[b] for the listed images (dst dense, src with its own batch stride)
@@ -302,6 +340,29 @@ extern "C" int drag_stepcache_copy_images_bf16(void* dst_dense, const void* src,
              "drag_stepcache_copy_images_bf16: images must be a host array of strictly increasing indices in [0, B)");
   hipLaunchKernelGGL(stepcache_copy_images_kernel, dim3(sc_blocks_per_image(n_images, n / 8), n_images), dim3(SC_THREADS), 0,
                      (hipStream_t)stream, (bf16_t*)dst_dense, (const bf16_t*)src, n / 8, (long long)src_batch_stride, list);
+  DRAG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int drag_stepcache_forecast_images_bf16(void* x, const void* r, const void* p, int32_t B, int32_t rows_per_batch, int32_t cols,
+                                                   int64_t x_batch_stride, const int32_t* images, const float* coef, int32_t n_images,
+                                                   void* stream) {
+  SC_COMMON_CHECKS("drag_stepcache_forecast_images_bf16", x, r, x_batch_stride);
+  DRAG_CHECK(p && sc_aligned16(p), "drag_stepcache_forecast_images_bf16: p must be a 16-byte aligned pointer");
+  DRAG_CHECK(n_images >= 0 && n_images <= SC_MAX_LIST, "drag_stepcache_forecast_images_bf16: n_images must be in 0..64");
+  if (n_images == 0) return 0;
+  ScList list;
+  DRAG_CHECK(sc_take_list(images, n_images, B, true, &list),
+             "drag_stepcache_forecast_images_bf16: images must be a host array of strictly increasing indices in [0, B)");
+  DRAG_CHECK(coef, "drag_stepcache_forecast_images_bf16: coef must be a host array of n_images floats");
+  ScCoef cf;
+  for (int i = 0; i < SC_MAX_LIST; ++i) cf.v[i] = 0.0f;
+  for (int i = 0; i < n_images; ++i) {
+    DRAG_CHECK(isfinite(coef[i]), "drag_stepcache_forecast_images_bf16: every coefficient must be finite");
+    cf.v[i] = coef[i];
+  }
+  hipLaunchKernelGGL(stepcache_forecast_images_kernel, dim3(sc_blocks_per_image(n_images, n / 8), n_images), dim3(SC_THREADS), 0,
+                     (hipStream_t)stream, (bf16_t*)x, (const bf16_t*)r, (const bf16_t*)p, n / 8, (long long)x_batch_stride, list, cf);
   DRAG_LAUNCH_CHECK();
   return 0;
 }

@@ -187,13 +187,17 @@ class Engine:
 
     def __init__(self, kind: str, model_root: str = "./model", synthetic: bool = False, tiny: bool = False, device="cuda",
                  seed: int = 0, text_encoder: str = "transformers", linear_precision: str | None = None, step_cache: float | None = None,
-                 step_cache_scope: str | None = None):
+                 step_cache_scope: str | None = None, step_cache_order: int | None = None, step_cache_max_run: int | None = None,
+                 step_cache_warmup: int | None = None):
         """``text_encoder``: what encodes a prompt-cache miss — "transformers" (the reference's modules, eager torch) or "hip"
         (:mod:`.textenc`; with ``synthetic``: seeded encoders and stand-in tokenizers, results kept in memory).
         ``linear_precision``: the DiT blocks' Linears, "bf16" or "mxfp8" (None: $DRAG_LINEAR_PRECISION, else bf16; :mod:`.flux`).
         ``step_cache``: threshold of the first-block step cache of the denoise loop (:class:`.step_cache.StepCache`; None: $DRAG_STEP_CACHE, else
         off; 0: off) — the pipeline's ``step_cache`` attribute; ``step_cache_scope``: who decides a reuse, "batch" (the whole batch) or
-        "image" (every image for itself; None: $DRAG_STEP_CACHE_SCOPE, else "batch") — the pipeline's ``step_cache_scope``"""
+        "image" (every image for itself; None: $DRAG_STEP_CACHE_SCOPE, else "batch") — the pipeline's ``step_cache_scope``;
+        ``step_cache_order``: what a reused step adds, 0 (the cached residual) or 1 (its first-order forecast); ``step_cache_max_run`` /
+        ``step_cache_warmup``: after that many reused steps in a row the next one computes / the first that many steps compute (0: no
+        limit; None: $DRAG_STEP_CACHE_ORDER / _MAX_RUN / _WARMUP, else 0) — the pipeline's attributes of the same names"""
         assert kind in ("dev", "fill")
         if text_encoder not in ("transformers", "hip"):
             raise ValueError(f"text_encoder must be 'transformers' or 'hip', not {text_encoder!r}")
@@ -224,7 +228,9 @@ class Engine:
         del tp, vp
         self.cfg, self.vit_cfg = cfg, vitcfg
         self.prior = redux_mod.ReduxPriorHIP(vitcfg, vitp, rp, dev)
-        self.pipe = (FluxFillHIP if kind == "fill" else FluxTxt2ImgHIP)(tr, vae, step_cache=step_cache, step_cache_scope=step_cache_scope)
+        self.pipe = (FluxFillHIP if kind == "fill" else FluxTxt2ImgHIP)(
+            tr, vae, step_cache=step_cache, step_cache_scope=step_cache_scope, step_cache_order=step_cache_order,
+            step_cache_max_run=step_cache_max_run, step_cache_warmup=step_cache_warmup)
         Lt, J, P = TINY["t5_tokens"] if tiny else redux_mod.T5_TOKENS, cfg.joint_attention_dim, cfg.pooled_projection_dim
         if text_encoder == "hip" and synthetic:
             self.text = TextCache(model_root, False, Lt, J, P, dev, persist=False,

@@ -24,8 +24,9 @@ import torch
 
 from . import ops
 from .flux_params import FluxConfig
-from .step_cache import (STEP_CACHE_DEFAULT, STEP_CACHE_SCOPE_DEFAULT, STEP_CACHE_SCOPES, StepCache, StepDecision, compact_pairs,      # noqa: F401
-                         parse_step_cache, parse_step_cache_scope, pipeline_step_cache)
+from .step_cache import (STEP_CACHE_DEFAULT, STEP_CACHE_MAX_RUN_DEFAULT, STEP_CACHE_ORDER_DEFAULT, STEP_CACHE_SCOPE_DEFAULT,      # noqa: F401
+                         STEP_CACHE_SCOPES, STEP_CACHE_WARMUP_DEFAULT, StepCache, StepDecision, compact_pairs, forecast_coefficient,
+                         parse_step_cache, parse_step_cache_count, parse_step_cache_order, parse_step_cache_scope, pipeline_step_cache)
 
 _SEPARATE_QPREP = os.environ.get("DRAG_QPREP_SEPARATE", "") not in ("", "0")     # measurement switches, read once
 # single blocks: to_q|k|v + proj_mlp as ONE two-destination launch.  At the headline's 42 696 rows it saves a partial tile round
@@ -375,7 +376,8 @@ class FluxTransformerHIP:
         """hidden bf16 [B, S_img, in]; enc bf16 [B, S_txt, J]; pooled bf16 [B, P]; timestep / guidance
         fp32 [B] host or device; returns bf16 [B, S_img, out] (a view of an internal workspace).
         ``cache``: a :class:`StepCache` (opt-in; None is the plain forward, the same launches in the same order): after the first double block the
-        step (scope "image": each image) reuses the cached residual of the remaining blocks, or computes them and refreshes the cache."""
+        step (scope "image": each image) reuses the cached residual of the remaining blocks (order 1: its first-order forecast along ``timestep``),
+        or computes them and refreshes the cache."""
         cfg = self.cfg
         if cache is not None and (cfg.num_layers < 1 or cfg.num_layers + cfg.num_single_layers < 2):
             raise ValueError("a step cache needs a double block and at least one further block")
@@ -402,9 +404,12 @@ class FluxTransformerHIP:
                  c_rows_per_batch=St, c_batch_stride=S * D, ldc=D)
         if cfg.guidance_embeds and guidance is None:
             raise ValueError("this model has a guidance embedding: pass guidance")
+        times = None                  # the host timesteps, for a step cache of order 1
         if timestep is not None:      # eager call: refresh the device-side times (a replayed graph gets them from forward_graphed)
-            self._set_times(torch.as_tensor(timestep, dtype=torch.float32).cpu().reshape(-1),
-                            None if guidance is None else torch.as_tensor(guidance, dtype=torch.float32).cpu().reshape(-1))
+            t_host = torch.as_tensor(timestep, dtype=torch.float32).cpu().reshape(-1)
+            self._set_times(t_host, None if guidance is None else torch.as_tensor(guidance, dtype=torch.float32).cpu().reshape(-1))
+            if cache is not None:
+                times = t_host.tolist()
         temb = self._temb(pooled, cfg.guidance_embeds)
         st = ops.act(temb, ops.ACT_SILU)
         ops.gemm(st, self.mod_w, out=mod, bias=self.mod_b)          # every block's modulation in one GEMM
@@ -421,7 +426,7 @@ class FluxTransformerHIP:
                 cache.before_first_block(x, B, St, Si, D, self._linear_precision, self.device)
             self._double_block(ws, 0, B, St, Si, cos, sin, taps)
             if cache is not None:
-                nb = cache.after_first_block(x, mod, B, St, Si, D, taps)
+                nb = cache.after_first_block(x, mod, B, St, Si, D, taps, times=times)
         if nb:
             self._blocks_after_first(ws, nb, St, Si, cos, sin, taps)
         if cache is not None:

@@ -638,6 +638,26 @@ def stepcache_copy_images(dst: torch.Tensor, src: torch.Tensor, src_batch_stride
           "drag_stepcache_copy_images_bf16")
 
 
+def stepcache_forecast_images(x: torch.Tensor, r: torch.Tensor, p: torch.Tensor, B: int, rows_per_batch: int, cols: int, x_batch_stride: int,
+                              images, coefs) -> None:
+    """the first-order forecast of a reused step on the images listed in ``images`` (as in ``stepcache_apply_images``), image ``images[i]``
+    with the coefficient ``coefs[i]`` (host floats, passed as float32, all finite): per element ``d = f32(r) - f32(p); m = c * d;
+    f = m + f32(r); x <- bf16(f32(x) + f)``, four individually rounded float32 operations, no FMA
+    (``drag_stepcache_forecast_images_bf16``).  ``r`` and ``p`` are dense [B, rows_per_batch, cols], indexed by image, and stay as they
+    are.  An empty list launches nothing."""
+    lib = _lib.load()
+    _need(x, torch.bfloat16, "stepcache_forecast_images.x")
+    _need(r, torch.bfloat16, "stepcache_forecast_images.r")
+    _need(p, torch.bfloat16, "stepcache_forecast_images.p")
+    arr, n = _index_list(images)
+    c = [float(v) for v in coefs]
+    if len(c) != n:
+        raise ValueError(f"stepcache_forecast_images: {n} images but {len(c)} coefficients")
+    _stepcache_room(x, dict(r=r, p=p), B, rows_per_batch, cols, x_batch_stride, "stepcache_forecast_images")
+    check(lib.drag_stepcache_forecast_images_bf16(_p(x), _p(r), _p(p), B, rows_per_batch, cols, x_batch_stride, arr,
+                                                  (ctypes.c_float * max(1, n))(*c), n, _stream()), "drag_stepcache_forecast_images_bf16")
+
+
 def _dense_operand(t: torch.Tensor, n: int, name: str, exact: bool = False) -> None:
     """a further operand of an elementwise kernel that walks ``n`` dense bf16 elements: a GPU bf16 tensor whose own ``n`` elements (at
     least ``n``, or with ``exact`` just ``n``) lie dense in its storage — anything else is an error here, not a memory fault in the kernel"""

@@ -319,6 +319,17 @@ int drag_stepcache_apply_images_bf16(void* x, void* r, int32_t B, int32_t rows_p
                                      int32_t sign, const int32_t* images, int32_t n_images, void* stream);
 int drag_stepcache_copy_images_bf16(void* dst_dense, const void* src, int64_t src_batch_stride, int32_t B, int32_t rows_per_batch,
                                     int32_t cols, const int32_t* images, int32_t n_images, void* stream);
+/* drag_stepcache_forecast_images_bf16 — the first-order forecast of a reused step (StepCache order = 1): r is the remaining-blocks
+ * residual of the image's last computed step, p that of the computed step before it, both dense [B, rows_per_batch, cols] and indexed by
+ * image; for each listed image b = images[i] with c = coef[i] = (t_now - t_last) / (t_last - t_prev), per element of its rows of x, in place
+ *   d = f32(r) - f32(p);   m = c * d;   f = m + f32(r);   s = f32(x) + f;   x <- bf16 round-to-nearest-even(s)
+ * — four individually rounded float32 operations, m + r NOT contracted into an FMA (a numpy float32 restatement gives the same bits);
+ * NaN and infinities propagate as IEEE says; r and p are only read.  `images` and `coef` are HOST arrays of n_images entries, copied into
+ * the kernel's argument struct.  x is addressed and everything validated as in drag_stepcache_apply_images_bf16 (p as r); in addition
+ * every coef[i] must be finite.  A refused call returns -1 and launches nothing; an empty list is a successful no-op without a launch.
+ * Grid shape, grid-stride remainder and workgroups per image are those of drag_stepcache_apply_images_bf16. */
+int drag_stepcache_forecast_images_bf16(void* x, const void* r, const void* p, int32_t B, int32_t rows_per_batch, int32_t cols,
+                                        int64_t x_batch_stride, const int32_t* images, const float* coef, int32_t n_images, void* stream);
 
 /* elementwise helpers (bf16) */
 int drag_act_bf16(const void* x, void* y, int64_t n, int32_t act, void* stream);

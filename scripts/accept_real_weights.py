@@ -268,6 +268,9 @@ def _hip_pipes(args, kind, encoders):
     if getattr(args, "step_cache", None):       # --step-cache: the HIP side runs with the first-block step cache (step_cache.StepCache)
         pipe.pipe.step_cache = args.step_cache
         pipe.pipe.step_cache_scope = getattr(args, "step_cache_scope", None) or "batch"
+        pipe.pipe.step_cache_order = getattr(args, "step_cache_order", None) or 0
+        pipe.pipe.step_cache_max_run = getattr(args, "step_cache_max_run", None) or 0
+        pipe.pipe.step_cache_warmup = getattr(args, "step_cache_warmup", None) or 0
     return prior, pipe
 
 
@@ -359,6 +362,12 @@ def main(argv=None) -> int:
                     help="run the HIP stage-2 / stage-3 pipelines with the first-block step cache at this threshold (default: off)")
     ap.add_argument("--step-cache-scope", choices=["batch", "image"], default="batch",
                     help="with --step-cache: the batch decides a reuse as a whole, or every image for itself (default: batch)")
+    ap.add_argument("--step-cache-order", type=int, choices=[0, 1], default=0,
+                    help="with --step-cache: a reused step adds the cached residual (0) or its first-order forecast (1) (default: 0)")
+    ap.add_argument("--step-cache-max-run", type=int, default=0, metavar="N",
+                    help="with --step-cache: after N reused steps in a row the next one computes (default: 0, no limit)")
+    ap.add_argument("--step-cache-warmup", type=int, default=0, metavar="N",
+                    help="with --step-cache: the first N steps compute (default: 0)")
     args = ap.parse_args(argv)
     sections = [s for s in args.sections.split(",") if s]
     bad = [s for s in sections if s not in SECTIONS]
@@ -371,6 +380,11 @@ def main(argv=None) -> int:
         report["step_cache"] = args.step_cache
         if args.step_cache_scope == "image":
             report["step_cache_scope"] = args.step_cache_scope
+        if args.step_cache_order == 1:
+            report["step_cache_order"] = args.step_cache_order
+        for name in ("step_cache_max_run", "step_cache_warmup"):
+            if getattr(args, name) > 0:
+                report[name] = getattr(args, name)
     if any(s in sections for s in ("stage2", "stage3")) and not args.target:
         report["missing"].append("--target <inpainted k-shot image>")
     if report["missing"]:

@@ -17,7 +17,12 @@ also timed alone at the workload's shape.  The weights are seeded random: the ra
 the remaining blocks at batch k): per step, a forced pattern in which the LAST k images compute (the most swaps) under scope "image"
 against the same pattern under scope "batch", where any computing image makes all B compute.  Passes k = 0, B/4, B/2, 3B/4, B under
 "image" and k = 0, B under "batch", interleaved round by round in one process; the swaps and list kernels of a mixed step are also timed
-alone.  Writes step_cache_image.json and step_cache_image.log."""
+alone.  Writes step_cache_image.json and step_cache_image.log.
+
+``--order 1`` measures the first-order forecast of a reused step (``StepCache(order=1)``) against order 0: the forced patterns "every 2nd"
+and "every 3rd step computed", each at order 0 and order 1, and the off pass, interleaved round by round in one process — wall per
+batch, the reused step's GPU time, the distance of the final latents from the off pass — and the forecast kernel next to ``apply(+1)``
+alone.  Writes step_cache_forecast.json and step_cache_forecast.log."""
 import argparse
 import json
 import math
@@ -42,7 +47,10 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=2, help="timed rounds; every round runs each pass once, in order (one warm-up round first)")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
     ap.add_argument("--scope", choices=["batch", "image"], default="batch", help="image: measure mixed steps of the cache's scope \"image\"")
+    ap.add_argument("--order", type=int, choices=[0, 1], default=0, help="1: measure the first-order forecast of a reused step against order 0")
     args = ap.parse_args(argv)
+    if args.order == 1:
+        return main_order(args)
     if args.scope == "image":
         return main_image(args)
     dev = torch.device("cuda:0")
@@ -277,6 +285,132 @@ def main_image(args):
         summary["passes"][name]["vs_all_compute_per_round"] = per_round
         say(f"{name:10s} {statistics.median(steps(name)):8.2f} ms  (x all-compute, per round: " + ", ".join(f"{v:.3f}" for v in per_round) + ")")
     with open(os.path.join(args.out_dir, "step_cache_image.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+        f.write("\n")
+    log.close()
+
+
+def main_order(args):
+    dev = torch.device("cuda:0")
+    n, B = args.denoise_steps, args.batch
+    job = SyntheticFillJob(batch=B, res=args.res, denoise_steps=n, device=dev)
+    # pass -> (order, forced): forced[i] is the value `reused` takes in step i; None = the cache is off
+    patterns = {"every_2nd": [i % 2 != 0 for i in range(n)], "every_3rd": [i % 3 != 0 for i in range(n)]}
+    passes = {"off": (0, None)}
+    for pname, forced in patterns.items():
+        for order in (0, 1):
+            passes[f"{pname}_order{order}"] = (order, forced)
+    os.makedirs(args.out_dir, exist_ok=True)
+    log = open(os.path.join(args.out_dir, "step_cache_forecast.log"), "w")
+
+    def say(s=""):
+        print(s, flush=True)
+        log.write(s + "\n"); log.flush()
+
+    def run(name):
+        order, forced = passes[name]
+        job.fill.step_cache, job.fill.step_cache_forced = (None if forced is None else math.inf), forced
+        job.fill.step_cache_scope, job.fill.step_cache_forced_images, job.fill.step_cache_order = "batch", None, order
+        marks, last = [], {}
+
+        def on_step(i, latents):
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            marks.append(ev)
+            last["latents"] = latents
+        pe, pp = job.prior(job.bg, job.t5, job.pooled, [job.ips], [1.0], group=1)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        job.fill(job.image, job.mask, pe, pp, guidance_scale=job.guidance, num_inference_steps=n, strength=job.strength,
+                 enc_noise=job.enc_noise, masked_enc_noise=job.menc_noise, noise_tokens=job.noise_tokens, on_step=on_step)
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        step_ms = [None] + [marks[i - 1].elapsed_time(marks[i]) for i in range(1, len(marks))]
+        reused = [False] * n if forced is None else [bool(d.reused) for d in job.fill.last_step_decisions]
+        fc = job.fill.last_step_forecasts
+        return dict(wall_s=wall, reused_ms=[t for t, u in zip(step_ms, reused) if t is not None and u], latents=last["latents"],
+                    forecast_steps=0 if fc is None else sum(1 for f in fc if f[0] is not None),
+                    coefficients=None if fc is None else [f[0] for f in fc])
+
+    say(f"# bench_step_cache --order 1: B = {B}, {args.res}^2, {n} steps, {args.rounds} timed rounds after one warm-up round; seeded random weights")
+    say(f"# device: {torch.cuda.get_device_name(0)}")
+    results = {k: [] for k in passes}
+    for rnd in range(args.rounds + 1):
+        for name in passes:
+            r = run(name)
+            if rnd == 0:
+                continue
+            results[name].append(r)
+            ru = r["reused_ms"]
+            say(f"round {rnd} {name:18s} wall {r['wall_s']:7.3f} s/batch  reused steps {len(ru):2d} (forecast on {r['forecast_steps']:2d})"
+                + (f"  median {statistics.median(ru):7.3f} ms (min {min(ru):7.3f}, max {max(ru):7.3f})" if ru else ""))
+
+    # ---- the forecast kernel next to apply(+1), alone, at the workload's shape (the joint buffer's addressing: text rows in front)
+    Si, St, D = job.Si, job.St, job.cfg.dim
+    S = St + Si
+    x = torch.randn((B, S, D), device=dev).bfloat16()
+    R, P = (torch.randn((B, Si, D), device=dev).bfloat16() for _ in range(2))
+    x_img = x.view(-1)[St * D:]
+    every, coefs = list(range(B)), [1.0 + 0.125 * b for b in range(B)]
+
+    def timed(fn, reps=20):
+        for _ in range(3):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+    mb = B * Si * D * 2 / 1e6
+    kern = {}
+    for rep in range(3):          # three alternating measurements of each
+        for k, fn, traffic in (("stepcache_apply +1 (reads x, r, writes x)", lambda: ops.stepcache_apply(x_img, R, B, Si, D, S * D, +1), 3 * mb),
+                               ("stepcache_forecast_images (reads x, r, p, writes x)",
+                                lambda: ops.stepcache_forecast_images(x_img, R, P, B, Si, D, S * D, every, coefs), 4 * mb)):
+            x.normal_()           # keep x finite over the repetitions
+            kern.setdefault(k, dict(ms=[], traffic_mb=traffic))["ms"].append(timed(fn))
+    say()
+    say(f"# kernels alone, B = {B}, {Si} x {D} image rows per batch inside [{B}, {S}, {D}] ({mb:.0f} MB per operand), 3 x 20 launches each")
+    for k, v in kern.items():
+        ms = statistics.median(v["ms"])
+        say(f"{k:54s} {ms:7.4f} ms median (min {min(v['ms']):.4f}, max {max(v['ms']):.4f})  {v['traffic_mb'] / ms / 1e3:6.2f} TB/s")
+    ka, kf = (statistics.median(v["ms"]) for v in kern.values())
+    say(f"forecast / apply: {kf / ka:.3f} (4/3 by the operands read and written)")
+
+    # ---- summary: order 1 against the order-0 pass of the same run; distances from the off pass, recorded without a claim
+    off = results["off"][-1]["latents"].double()
+    off_rms = off.pow(2).mean().sqrt().item()
+    summary = {"config": dict(batch=B, res=args.res, denoise_steps=n, rounds=args.rounds, device=torch.cuda.get_device_name(0), weights="seeded random"),
+               "kernels_ms": {k: v["ms"] for k, v in kern.items()}, "forecast_over_apply": kf / ka, "passes": {}}
+    say()
+    say("# per pass: wall per batch and reused step over all timed rounds; rms distance of the last round's final latents from the off pass, relative")
+    for name in passes:
+        rs = results[name]
+        walls = [r["wall_s"] for r in rs]
+        ru = [t for r in rs for t in r["reused_ms"]]
+        rel = (rs[-1]["latents"].double() - off).pow(2).mean().sqrt().item() / off_rms
+        summary["passes"][name] = dict(order=passes[name][0], wall_s_per_batch=walls, wall_s_median=statistics.median(walls), wall_s_min=min(walls),
+                                       wall_s_max=max(walls), reused_steps=len(rs[-1]["reused_ms"]), forecast_steps=rs[-1]["forecast_steps"],
+                                       reused_step_ms_median=statistics.median(ru) if ru else None, reused_step_ms_min=min(ru) if ru else None,
+                                       reused_step_ms_max=max(ru) if ru else None, final_latents_rms_rel_vs_off=rel, coefficients=rs[-1]["coefficients"])
+        say(f"{name:18s} wall {statistics.median(walls):7.3f} s/batch (min {min(walls):7.3f}, max {max(walls):7.3f})"
+            + (f"  reused step {statistics.median(ru):7.3f} ms (min {min(ru):7.3f}, max {max(ru):7.3f})" if ru else " " * 53)
+            + f"  latents rms vs off, relative {rel:.4e}")
+    say()
+    say("# order 1 - order 0, same pattern, same run (the order-0 pass is the reference; its own min-max spread next to it)")
+    for pname in patterns:
+        a, b = summary["passes"][f"{pname}_order0"], summary["passes"][f"{pname}_order1"]
+        d_wall, d_step = b["wall_s_median"] - a["wall_s_median"], b["reused_step_ms_median"] - a["reused_step_ms_median"]
+        spread_wall, spread_step = a["wall_s_max"] - a["wall_s_min"], a["reused_step_ms_max"] - a["reused_step_ms_min"]
+        summary["passes"][f"{pname}_order1"]["vs_order0"] = dict(wall_s=d_wall, wall_s_spread_of_order0=spread_wall, reused_step_ms=d_step,
+                                                               reused_step_ms_spread_of_order0=spread_step)
+        say(f"{pname:10s} wall {d_wall:+8.4f} s/batch (order 0 spread {spread_wall:.4f})  reused step {d_step:+8.4f} ms (order 0 spread {spread_step:.4f})"
+            f"  {'within' if abs(d_wall) <= spread_wall else 'OUTSIDE'} the wall spread, {'within' if abs(d_step) <= spread_step else 'OUTSIDE'} the step spread")
+    say()
+    say("# the weights are seeded random and adjacent steps differ by first-block ratios of 0.4 - 0.6: the distances above say nothing about real checkpoints")
+    with open(os.path.join(args.out_dir, "step_cache_forecast.json"), "w") as f:
         json.dump(summary, f, indent=1)
         f.write("\n")
     log.close()
