@@ -180,6 +180,9 @@ static int attention_launch(const void* q, const void* k, const void* vt, void* 
   DRAG_CHECK(q && k && vt && out, "drag_attention_bf16: null pointer");
   DRAG_CHECK(B > 0 && S > 0 && H > 0, "drag_attention_bf16: bad shape");
   DRAG_CHECK(ld_qk % 8 == 0 && ld_o % 4 == 0, "drag_attention_bf16: ld_qk %% 8, ld_o %% 4 required");
+  // (the prep entry points' analogue is ld >= 3 H 128: a row holds every head; shorter output rows would overlap)
+  DRAG_CHECK(ld_qk >= H * 128, "drag_attention_bf16: ld_qk >= H * 128 required");
+  DRAG_CHECK(ld_o >= H * 128, "drag_attention_bf16: ld_o >= H * 128 required");
   AttnArgs p;
   p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.vt = (const bf16_t*)vt; p.v = (const bf16_t*)vt; p.out = (bf16_t*)out;
   p.B = B; p.S = S; p.H = H; p.ld_qk = ld_qk; p.ld_o = ld_o; p.s_pad = (S + 63) / 64 * 64;

@@ -427,13 +427,79 @@ def gemm_mxfp8(aq: torch.Tensor, ascale: torch.Tensor, wq: torch.Tensor, wscale:
     return out
 
 
+def _attention_reach(kind: str, B: int, S: int, H: int, ld: int = 0, batch_stride: int = 0) -> int:
+    """elements, counted from an operand's first one, that the head_dim-128 attention path addresses (one more than the largest offset; pure
+    integers, tests/test_attention_room_host.py enumerates the addresses).  ``kind``: "rows" = q, k, row-major v or ``out`` (row s of batch b at
+    b * batch_stride + s * ld, head h at + 128 h); "vt" = the V^T image; "prep" = the prep pass's qkv (batch b at b * S * ld, q | k | v side by
+    side in a row); "rope" = one RoPE table (f32); "norm" = one RMSNorm weight"""
+    if kind == "rows":
+        return (B - 1) * batch_stride + (S - 1) * ld + H * 128
+    if kind == "vt":
+        return B * H * 128 * ((S + 63) // 64 * 64)
+    if kind == "prep":
+        return (B * S - 1) * ld + 3 * H * 128
+    if kind == "rope":
+        return S * 64
+    if kind == "norm":
+        return 128
+    raise KeyError(kind)
+
+
+def _attention_room(what: str, B: int, S: int, H: int, rows=(), vt=None, prep=None, ropes=(), norms=()) -> None:
+    """the operands of one of the five head_dim-128 attention wrappers before the launch: every optional one a GPU tensor of its dtype, no
+    negative stride, output rows that do not overlap, and the last element each operand's addressing reaches (``_attention_reach``) inside
+    its storage — a wrong stride is an error here, not a memory fault in the kernel (shapes the library refuses — ld % 8, ld_o % 4, the
+    2 GiB K span, B / S / H <= 0 — stay the library's to report).  ``rows``: (name, tensor, ld, batch_stride); ``prep``: (tensor, ld);
+    ``ropes`` / ``norms``: (name, tensor or None)"""
+    for group, dtype in ((ropes, torch.float32), (norms, torch.bfloat16)):
+        for name, t in group:
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype):
+                raise ValueError(f"{what}.{name}: expected a GPU {dtype} tensor, got {getattr(t, 'dtype', type(t))}"
+                                 f"{'' if getattr(t, 'is_cuda', True) else ' on the host'}")
+    if B <= 0 or S <= 0 or H <= 0:
+        return
+    for name, t, ld, bs in rows:
+        if ld < 0 or bs < 0:
+            raise ValueError(f"{what}.{name}: negative stride (row stride {ld}, batch stride {bs})")
+        if name == "out" and ld < H * 128:
+            raise ValueError(f"{what}.out: rows of stride {ld} overlap ({H} heads x 128 = {H * 128} elements each)")
+        reach = _attention_reach("rows", B, S, H, ld, bs)
+        if reach > _room(t):
+            raise ValueError(f"{what}.{name}: {B} x {S} rows of {H * 128} (row stride {ld}, batch stride {bs}) reach element {reach} of "
+                             f"{_room(t)} from its start")
+    if vt is not None and _attention_reach("vt", B, S, H) > _room(vt):
+        raise ValueError(f"{what}.vt: [B, H, 128, s_pad] with s_pad = {(S + 63) // 64 * 64} (S rounded up to 64) is "
+                         f"{_attention_reach('vt', B, S, H)} elements, got {_room(vt)} from its start")
+    if prep is not None:
+        t, ld = prep
+        if ld < 0:
+            raise ValueError(f"{what}.qkv: negative row stride {ld}")
+        if _attention_reach("prep", B, S, H, ld) > _room(t):
+            raise ValueError(f"{what}.qkv: {B * S} rows of stride {ld} (batch b at b * S * ld) reach element "
+                             f"{_attention_reach('prep', B, S, H, ld)} of {_room(t)} from its start")
+    for group, kind in ((ropes, "rope"), (norms, "norm")):
+        for name, t in group:
+            if t is not None and _attention_reach(kind, B, S, H) > _room(t):
+                raise ValueError(f"{what}.{name}: expected at least {_attention_reach(kind, B, S, H)} elements, got {_room(t)} from its start")
+
+
 def qk_norm_rope_vt(qkv: torch.Tensor, vt: torch.Tensor, wq_txt, wk_txt, wq_img, wk_img, rope_cos, rope_sin,
                     B: int, S: int, H: int, ld: int, s_txt: int, eps: float = 1e-6) -> None:
+    """The pass in front of ``attention`` (``drag_qk_norm_rope_vt_bf16``): per-head RMSNorm (weights ``w*_txt`` [128] for rows < ``s_txt``,
+    ``w*_img`` after; all four or none) and RoPE (``rope_cos`` / ``rope_sin`` f32 [S, 64]; both or neither) of q and k IN PLACE, and V -> V^T.
+
+    ``qkv`` is a view whose first element is q of token 0 of batch 0, 16-byte aligned: token s of batch b lies at (b * S + s) * ld, its q | k | v
+    at + 0 | H*128 | 2*H*128 (``ld`` >= 3*H*128, a multiple of 8; the columns beyond belong to the caller and are not touched, nor is v).  The
+    pass has NO batch-stride argument: batch b starts at b * S * ld from the view's start, whatever lies between the rows.
+
+    ``vt`` is the dense [B, H, 128, s_pad] image, s_pad = S rounded up to a multiple of 64, every element of which is written: inside each
+    group of 16 keys, position 16g + w of row d holds V[16g + 8*((w >> 2) & 1) + 4*(w >> 3) + (w & 3)][d] (the order in which a lane of the
+    attention kernels holds its P registers), and positions whose key is >= S hold +0.0."""
     lib = _lib.load()
     _need(qkv, torch.bfloat16, "qkv")
     _need(vt, torch.bfloat16, "vt")
-    if rope_cos is not None:
-        _need(rope_cos, torch.float32, "rope_cos")
+    _attention_room("qk_norm_rope_vt", B, S, H, vt=vt, prep=(qkv, ld), ropes=(("rope_cos", rope_cos), ("rope_sin", rope_sin)),
+                    norms=(("wq_txt", wq_txt), ("wk_txt", wk_txt), ("wq_img", wq_img), ("wk_img", wk_img)))
     check(lib.drag_qk_norm_rope_vt_bf16(_p(qkv), _p(vt), _p(wq_txt), _p(wk_txt), _p(wq_img), _p(wk_img),
                                         _p(rope_cos), _p(rope_sin), B, S, H, ld, s_txt, eps, _stream()),
           "drag_qk_norm_rope_vt_bf16")
@@ -441,20 +507,43 @@ def qk_norm_rope_vt(qkv: torch.Tensor, vt: torch.Tensor, wq_txt, wk_txt, wq_img,
 
 def attention(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, B: int, S: int, H: int,
               ld_qk: int, qk_batch_stride: int, ld_o: int, o_batch_stride: int, scale: float) -> None:
+    """head_dim-128 attention over prepared q and k and the V^T image of ``qk_norm_rope_vt`` (``drag_attention_bf16``).  The layout contract of
+    the attention wrappers (``attention_qprep`` and ``attention_v`` share it):
+
+    - ``q`` / ``k`` (and ``attention_v``'s row-major ``v``) are views whose first element is head 0 of token 0 of batch 0, each 16-byte aligned:
+      token s of batch b at b * qk_batch_stride + s * ld_qk, head h at + 128 h; ``ld_qk`` >= H*128 and a multiple of 8; one (batch, head)'s k
+      rows span less than 2 GiB.  The three share the row and batch stride; whatever lies between the rows is not read.
+    - ``out`` [B, S, H*128]: token s of batch b at b * o_batch_stride + s * ld_o, 8-byte aligned, ``ld_o`` >= H*128 and a multiple of 4; only
+      those B * S * H*128 elements are written.  The epilogue stores 16 bytes at a time when every output row is 16-byte aligned (``out``
+      16-byte aligned, ``ld_o`` and ``o_batch_stride`` multiples of 8, and "attn_tune" bit 2 set, the default) and 8 bytes at a time otherwise:
+      the same bits either way.
+    - ``vt`` is the dense [B, H, 128, s_pad] image, s_pad = S rounded up to a multiple of 64, in the key order ``qk_norm_rope_vt`` documents.
+    - RoPE tables are f32 [S, 64], norm weights bf16 [128].
+
+    An operand whose addressing would leave its storage, a negative stride or overlapping output rows raise ValueError before anything is
+    launched."""
     lib = _lib.load()
     _need(q, torch.bfloat16, "q")
+    _need(k, torch.bfloat16, "k")
+    _need(vt, torch.bfloat16, "vt")
     _need(out, torch.bfloat16, "out")
+    _attention_room("attention", B, S, H, rows=(("q", q, ld_qk, qk_batch_stride), ("k", k, ld_qk, qk_batch_stride), ("out", out, ld_o, o_batch_stride)),
+                    vt=vt)
     _recorded_attention(lambda: check(lib.drag_attention_bf16(_p(q), _p(k), _p(vt), _p(out), B, S, H, ld_qk, qk_batch_stride, ld_o,
                                                               o_batch_stride, scale, _stream()), "drag_attention_bf16"), B, S, H, False, False)
 
 
 def k_norm_rope_vt(qkv: torch.Tensor, vt: torch.Tensor, wk_txt, wk_img, rope_cos, rope_sin, B: int, S: int, H: int, ld: int,
                    s_txt: int, eps: float = 1e-6) -> None:
-    """k RMSNorm + RoPE in place and V -> V^T; q is left as projected (``attention_qprep`` prepares it on load)"""
+    """k RMSNorm + RoPE in place and V -> V^T; q is left as projected (``attention_qprep`` prepares it on load).  ``qkv``'s layout (batch b at
+    b * S * ld from the view's start: the pass has no other batch stride), ``vt``'s size and its key order are ``qk_norm_rope_vt``'s; with
+    ``vt`` None only k is prepared and v is not read."""
     lib = _lib.load()
     _need(qkv, torch.bfloat16, "qkv")
     if vt is not None:              # None: k only (``attention_v`` reads v row-major)
         _need(vt, torch.bfloat16, "vt")
+    _attention_room("k_norm_rope_vt", B, S, H, vt=vt, prep=(qkv, ld), ropes=(("rope_cos", rope_cos), ("rope_sin", rope_sin)),
+                    norms=(("wk_txt", wk_txt), ("wk_img", wk_img)))
     check(lib.drag_k_norm_rope_vt_bf16(_p(qkv), _p(vt), _p(wk_txt), _p(wk_img), _p(rope_cos), _p(rope_sin), B, S, H, ld, s_txt,
                                        eps, _stream()), "drag_k_norm_rope_vt_bf16")
 
@@ -462,12 +551,16 @@ def k_norm_rope_vt(qkv: torch.Tensor, vt: torch.Tensor, wk_txt, wk_img, rope_cos
 def attention_qprep(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, B: int, S: int, H: int, ld_qk: int,
                     qk_batch_stride: int, ld_o: int, o_batch_stride: int, scale: float, wq_txt, wq_img, rope_cos, rope_sin,
                     s_txt: int, eps: float = 1e-6) -> None:
-    """attention over the RAW q projection: norm_q + RoPE are applied to each query row as its fragments are loaded"""
+    """attention over the RAW q projection: norm_q + RoPE are applied to each query row as its fragments are loaded (weights ``wq_txt`` for
+    rows < ``s_txt``, ``wq_img`` after).  Layout contract: ``attention``'s."""
     lib = _lib.load()
     _need(q, torch.bfloat16, "q")
+    _need(k, torch.bfloat16, "k")
+    _need(vt, torch.bfloat16, "vt")
     _need(out, torch.bfloat16, "out")
-    if rope_cos is not None:
-        _need(rope_cos, torch.float32, "rope_cos")
+    _attention_room("attention_qprep", B, S, H,
+                    rows=(("q", q, ld_qk, qk_batch_stride), ("k", k, ld_qk, qk_batch_stride), ("out", out, ld_o, o_batch_stride)), vt=vt,
+                    ropes=(("rope_cos", rope_cos), ("rope_sin", rope_sin)), norms=(("wq_txt", wq_txt), ("wq_img", wq_img)))
     _recorded_attention(lambda: check(lib.drag_attention_qprep_bf16(_p(q), _p(k), _p(vt), _p(out), B, S, H, ld_qk, qk_batch_stride, ld_o,
                                                                     o_batch_stride, scale, _p(wq_txt), _p(wq_img), _p(rope_cos), _p(rope_sin),
                                                                     s_txt, eps, _stream()), "drag_attention_qprep_bf16"), B, S, H, True, False)
@@ -477,13 +570,16 @@ def attention_v(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Te
                 qk_batch_stride: int, ld_o: int, o_batch_stride: int, scale: float, wq_txt=None, wq_img=None, rope_cos=None,
                 rope_sin=None, s_txt: int = 0, eps: float = 1e-6) -> None:
     """attention over q | k | v as the Linears wrote them: v is read row-major (no V^T pass / buffer); the q preparation
-    (norm weights + RoPE tables) is optional"""
+    (norm weights + RoPE tables) is optional: all four or none.  Layout contract: ``attention``'s, ``v`` sharing q's and k's row stride and
+    batch stride (and their 16-byte alignment)."""
     lib = _lib.load()
     _need(q, torch.bfloat16, "q")
+    _need(k, torch.bfloat16, "k")
     _need(v, torch.bfloat16, "v")
     _need(out, torch.bfloat16, "out")
-    if rope_cos is not None:
-        _need(rope_cos, torch.float32, "rope_cos")
+    _attention_room("attention_v", B, S, H, rows=(("q", q, ld_qk, qk_batch_stride), ("k", k, ld_qk, qk_batch_stride),
+                                                  ("v", v, ld_qk, qk_batch_stride), ("out", out, ld_o, o_batch_stride)),
+                    ropes=(("rope_cos", rope_cos), ("rope_sin", rope_sin)), norms=(("wq_txt", wq_txt), ("wq_img", wq_img)))
     _recorded_attention(lambda: check(lib.drag_attention_v_bf16(_p(q), _p(k), _p(v), _p(out), B, S, H, ld_qk, qk_batch_stride, ld_o, o_batch_stride,
                                                                 scale, _p(wq_txt), _p(wq_img), _p(rope_cos), _p(rope_sin), s_txt, eps, _stream()),
                                       "drag_attention_v_bf16"), B, S, H, wq_txt is not None, True)

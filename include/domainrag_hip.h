@@ -234,6 +234,10 @@ int drag_qk_norm_rope_vt_bf16(void* qkv, void* vt, const void* wq_txt, const voi
  * Replaces F.scaled_dot_product_attention in FluxAttnProcessor2_0.
  *   q, k: [B, S, *] rows with row stride ld_qk (elements), head h at column h*128 from q / k.
  *   vt as written by drag_qk_norm_rope_vt_bf16.  out: [B, S, *] row stride ld_o, head h at column h*128.
+ *   Token s of batch b lies at b * qk_batch_stride + s * ld_qk from q / k and at b * o_batch_stride + s * ld_o from out.
+ *   q, k (and drag_attention_v_bf16's v) 16-byte aligned, ld_qk % 8 == 0; out 8-byte aligned, ld_o % 4 == 0; ld_qk, ld_o >= H*128
+ *   (refused otherwise).  Only the B * S * H*128 output elements are written: 16 bytes per store when out is 16-byte aligned and
+ *   ld_o and o_batch_stride are multiples of 8, 8 bytes per store otherwise (the same bits).  INTEGRATION.md has the whole contract.
  */
 int drag_attention_bf16(const void* q, const void* k, const void* vt, void* out, int32_t B,
                         int32_t S, int32_t H, int32_t ld_qk, int64_t qk_batch_stride, int32_t ld_o,
