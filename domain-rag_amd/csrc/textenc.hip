@@ -266,10 +266,10 @@ extern "C" int drag_textenc_attention_bf16(const void* q, const void* k, const v
 }
 
 extern "C" int drag_t5_rmsnorm_bf16(const void* x, const void* weight, void* y, int32_t M, int32_t D, float eps, void* stream) {
-  DRAG_CHECK(x && weight && y, "drag_t5_rmsnorm_bf16: null pointer");
   DRAG_CHECK(M >= 0 && D >= 8 && D % 8 == 0 && D <= RMS_IT * 512, "drag_t5_rmsnorm_bf16: need D % 8 == 0 and 8 <= D <= 4096");
+  if (M == 0) return 0;      // nothing to do: an empty tensor has no address to check
+  DRAG_CHECK(x && weight && y, "drag_t5_rmsnorm_bf16: null pointer");
   DRAG_CHECK(aligned16(x) && aligned16(weight) && aligned16(y), "drag_t5_rmsnorm_bf16: pointers must be 16-byte aligned");
-  if (M == 0) return 0;
   hipLaunchKernelGGL(t5_rmsnorm_kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)weight,
                      (bf16_t*)y, M, D, eps);
   DRAG_LAUNCH_CHECK();
@@ -277,11 +277,11 @@ extern "C" int drag_t5_rmsnorm_bf16(const void* x, const void* weight, void* y, 
 }
 
 extern "C" int drag_gated_new_gelu_bf16(const void* h, void* y, int64_t M, int32_t F, void* stream) {
-  DRAG_CHECK(h && y, "drag_gated_new_gelu_bf16: null pointer");
   DRAG_CHECK(M >= 0 && F >= 8 && F % 8 == 0, "drag_gated_new_gelu_bf16: need F % 8 == 0");
-  DRAG_CHECK(aligned16(h) && aligned16(y), "drag_gated_new_gelu_bf16: pointers must be 16-byte aligned");
   const long long n8 = (long long)M * (F / 8);
   if (n8 == 0) return 0;
+  DRAG_CHECK(h && y, "drag_gated_new_gelu_bf16: null pointer");
+  DRAG_CHECK(aligned16(h) && aligned16(y), "drag_gated_new_gelu_bf16: pointers must be 16-byte aligned");
   hipLaunchKernelGGL(gated_new_gelu_kernel, dim3(ew_blocks(n8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)h, (bf16_t*)y, n8,
                      F / 8);
   DRAG_LAUNCH_CHECK();
@@ -289,10 +289,10 @@ extern "C" int drag_gated_new_gelu_bf16(const void* h, void* y, int64_t M, int32
 }
 
 extern "C" int drag_quick_gelu_bf16(const void* x, void* y, int64_t n, void* stream) {
-  DRAG_CHECK(x && y, "drag_quick_gelu_bf16: null pointer");
   DRAG_CHECK(n >= 0 && n % 8 == 0, "drag_quick_gelu_bf16: need n % 8 == 0");
-  DRAG_CHECK(aligned16(x) && aligned16(y), "drag_quick_gelu_bf16: pointers must be 16-byte aligned");
   if (n == 0) return 0;
+  DRAG_CHECK(x && y, "drag_quick_gelu_bf16: null pointer");
+  DRAG_CHECK(aligned16(x) && aligned16(y), "drag_quick_gelu_bf16: pointers must be 16-byte aligned");
   hipLaunchKernelGGL(quick_gelu_kernel, dim3(ew_blocks(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (bf16_t*)y,
                      (long long)(n / 8));
   DRAG_LAUNCH_CHECK();
@@ -301,11 +301,11 @@ extern "C" int drag_quick_gelu_bf16(const void* x, void* y, int64_t n, void* str
 
 extern "C" int drag_embed_gather_bf16(const int64_t* ids, const void* table, const void* pos, void* out, int64_t rows, int32_t S,
                                       int32_t D, int64_t vocab, void* stream) {
-  DRAG_CHECK(ids && table && out, "drag_embed_gather_bf16: null pointer");
   DRAG_CHECK(rows >= 0 && S >= 1 && D >= 8 && D % 8 == 0 && vocab >= 1, "drag_embed_gather_bf16: need D % 8 == 0, S >= 1, vocab >= 1");
-  DRAG_CHECK(aligned16(table) && aligned16(out) && (!pos || aligned16(pos)), "drag_embed_gather_bf16: pointers must be 16-byte aligned");
   const long long n8 = (long long)rows * (D / 8);
   if (n8 == 0) return 0;
+  DRAG_CHECK(ids && table && out, "drag_embed_gather_bf16: null pointer");
+  DRAG_CHECK(aligned16(table) && aligned16(out) && (!pos || aligned16(pos)), "drag_embed_gather_bf16: pointers must be 16-byte aligned");
   hipLaunchKernelGGL(embed_gather_kernel, dim3(ew_blocks(n8)), dim3(256), 0, (hipStream_t)stream, ids, (const bf16_t*)table,
                      (const bf16_t*)pos, (bf16_t*)out, (long long)rows, S, D / 8, (long long)vocab);
   DRAG_LAUNCH_CHECK();

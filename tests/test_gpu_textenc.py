@@ -16,36 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 from bf16_bar import bar as _bar  # noqa: E402
-
-
-def _bf(x):
-    return x.float().bfloat16()
-
-
-def _attention_f64(qkv, B, S, H, rel, causal, eager, scale):
-    """the kernel's function with its rounding points, in float64 on the host"""
-    D = H * 64
-    x = qkv.double().view(B, S, 3, H, 64).permute(2, 0, 3, 1, 4)             # [3, B, H, S, 64]
-    q, k, v = x[0], x[1], x[2]
-    s = q @ k.transpose(-1, -2)
-    qi, ki = torch.arange(S)[:, None], torch.arange(S)[None, :]
-    bias = rel.double()[:, ki - qi + S - 1][None] if rel is not None else 0.0       # [1, H, S, S]
-    if eager:
-        s = _bf(s).double()
-        if scale != 1.0:
-            s = _bf(s * scale).double()
-        if rel is not None:
-            s = _bf(s + bias).double()
-    else:
-        s = s * scale + bias
-    if causal:
-        s = s.masked_fill(ki > qi, float("-inf"))
-    e = torch.exp(s - s.amax(-1, keepdim=True))
-    if eager:
-        o = _bf(e / e.sum(-1, keepdim=True)).double() @ v
-    else:
-        o = (_bf(e).double() @ v) / e.sum(-1, keepdim=True)
-    return _bf(o).permute(0, 2, 1, 3).reshape(B, S, D)
+from textenc_ref import attention_f64 as _attention_f64  # noqa: E402
 
 
 @pytest.mark.parametrize("eager", [True, False], ids=["eager_t5", "sdpa_clip"])

@@ -125,3 +125,17 @@ def test_abi_refuses_bad_arguments(built_lib):
     assert built_lib.drag_gated_new_gelu_bf16(p, p, 4, 12, None) != 0 and b"F % 8" in built_lib.drag_last_error()
     assert built_lib.drag_quick_gelu_bf16(p, p, 12, None) != 0 and b"n % 8" in built_lib.drag_last_error()
     assert built_lib.drag_embed_gather_bf16(None, p, None, p, 4, 4, 64, 10, None) != 0 and b"null" in built_lib.drag_last_error()
+
+
+def test_abi_accepts_calls_with_nothing_to_do(built_lib):
+    """an empty torch tensor has no address (data_ptr() is 0): a call over no rows is accepted before any pointer is looked at, so
+    ops.t5_rmsnorm / gated_new_gelu / quick_gelu / embed_gather take empty tensors; a bad width is refused all the same"""
+    buf = (ctypes.c_uint16 * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    assert built_lib.drag_t5_rmsnorm_bf16(None, p, None, 0, 768, 1e-6, None) == 0
+    assert built_lib.drag_gated_new_gelu_bf16(None, None, 0, 64, None) == 0
+    assert built_lib.drag_quick_gelu_bf16(None, None, 0, None) == 0
+    assert built_lib.drag_embed_gather_bf16(None, p, None, None, 0, 4, 64, 10, None) == 0
+    assert built_lib.drag_t5_rmsnorm_bf16(None, p, None, 0, 4104, 1e-6, None) != 0 and b"D <= 4096" in built_lib.drag_last_error()
+    assert built_lib.drag_gated_new_gelu_bf16(None, None, 0, 12, None) != 0 and b"F % 8" in built_lib.drag_last_error()
+    assert built_lib.drag_t5_rmsnorm_bf16(None, p, None, 4, 768, 1e-6, None) != 0 and b"null" in built_lib.drag_last_error()
