@@ -82,6 +82,11 @@ SIGNATURES = {
     "drag_attention_bf16_choice": (c_int, [c_int, c_int, c_int]),
     "drag_attention_bf16_kernel_name": (ctypes.c_char_p, [c_int, c_int, c_int]),
     "drag_attention_v_bf16": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_int64, c_int, c_int64, c_float] + [c_void_p] * 4 + [c_int, c_float, c_void_p]),
+    "drag_qkv_prep_mxfp8": (c_int, [c_void_p] * 7 + [c_int] * 5 + [c_float] + [c_void_p] * 7),
+    "drag_attention_mxfp8": (c_int, [c_void_p] * 7 + [c_int] * 4 + [c_int64, c_float, c_void_p]),
+    "drag_attention_mxfp8_s_pad": (c_int, [c_int]),
+    "drag_attention_mxfp8_supported": (c_int, [c_int, c_int, c_int]),
+    "drag_attention_mxfp8_kernel_name": (ctypes.c_char_p, [c_int]),
     "drag_layernorm_modulate_bf16": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_int64, c_int, c_int, c_float, c_void_p]),
     "drag_stepcache_workspace_bytes": (c_int64, [c_int] * 3),
     "drag_stepcache_delta_bf16": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_int64, c_void_p]),

@@ -13,6 +13,9 @@ def add_engine_arguments(p, batch_flag: str, steps: int, tiny: str, png_files: s
     p.add_argument("--linear_precision", choices=["bf16", "mxfp8"], default=None,
                    help="the DiT blocks' Linears: bf16, or OCP MXFP8 operands on the block-scaled matrix instruction (opt-in, lower "
                         "precision); default: $DRAG_LINEAR_PRECISION, else bf16")
+    p.add_argument("--attention_precision", choices=["bf16", "mxfp8"], default=None,
+                   help="the DiT blocks' attention: bf16, or OCP MXFP8 operands for both products (opt-in, lower precision: about 5 %% rms "
+                        "per attention against 0.2 %%); default: $DRAG_ATTENTION_PRECISION, else bf16")
     p.add_argument("--step_cache", type=parse_step_cache, default=None, metavar="THRESHOLD",
                    help="first-block step cache of the denoise loop (opt-in, lower fidelity): a step whose first-block residual moved by less "
                         "than THRESHOLD (relative L1, every image of the batch) since the last computed step reuses that step's remaining "
@@ -48,7 +51,12 @@ def pipe_step_cache_switches(pipe) -> tuple:
             getattr(pipe, "step_cache_max_run", 0), getattr(pipe, "step_cache_warmup", 0))
 
 
+def pipe_attention_precision(pipe) -> str:
+    """the attention precision of a pipeline's DiT, for the stages' two parameter writers"""
+    return getattr(getattr(pipe, "tr", None), "attention_precision", "bf16")
+
+
 def engine_from_args(kind: str, args, device) -> Engine:
     return Engine(kind, args.model_root, synthetic=args.synthetic_weights, tiny=args.tiny, device=device, text_encoder=args.text_encoder,
-                  linear_precision=args.linear_precision, step_cache=args.step_cache, step_cache_scope=args.step_cache_scope,
+                  linear_precision=args.linear_precision, attention_precision=args.attention_precision, step_cache=args.step_cache, step_cache_scope=args.step_cache_scope,
                   step_cache_order=args.step_cache_order, step_cache_max_run=args.step_cache_max_run, step_cache_warmup=args.step_cache_warmup)

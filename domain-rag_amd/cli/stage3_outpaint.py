@@ -28,7 +28,7 @@ import torch
 from .. import hostlogic as H
 from ..engine import Engine, generator_noise, pack_noise
 from ..io_pool import ImageWriter
-from .engine_args import add_engine_arguments, engine_from_args, pipe_step_cache_switches
+from .engine_args import add_engine_arguments, engine_from_args, pipe_attention_precision, pipe_step_cache_switches
 
 RESULT_DIR, DATASETS_DIR = "./result", "./datasets"
 
@@ -262,6 +262,8 @@ def process_sample(engine: Engine, args, dataset, sample_id, sample_dir, shot, p
                           "was_downscaled": wd, "bbox_coords_list": bboxes, "processed_bbox_coords_list": pb,
                           "image_id": info["id"] if info.get("id") is not None else "unknown", "num_bbox": len(bboxes)}
                 params.update(step_cache_params(*pipe_step_cache_switches(engine.pipe)))
+                if pipe_attention_precision(engine.pipe) == "mxfp8":      # (absent in bf16: the file is then the reference's)
+                    params["attention_precision"] = "mxfp8"
                 params_path = os.path.join(out_dir, f"{prefix}_params{suffix}.json")
                 with open(params_path, "w") as f:
                     json.dump(params, f, indent=2)

@@ -61,6 +61,52 @@ constexpr float DEFER_THR = 8.0f;     // log2 units; 0 = rescale on every increa
 constexpr int KT_BYTES = 64 * 256;   // K tile   [64 keys][128 d] bf16
 constexpr int VT_BYTES = 128 * 128;  // V^T tile [128 d][64 keys] bf16
 
+// ---- device code the two prep passes share (qk_norm_rope_vt_kernel and qkv_prep_mxfp8_kernel) ----
+// Per-head RMSNorm(128) + interleaved RoPE of one q (which = 0) or k (which = 1) row, 16 lanes per row: lane sub of the sixteen holds the raw
+// elements d = 8 sub + 0..7 and gets their prepared bf16 pairs back.  sc = the row (clamped to S - 1).  Every lane of the sixteen must call it.
+__device__ __forceinline__ u32x4_t qk_norm_rope8(const PrepArgs& p, const int which, const int sc, const int sub, const u32x4_t raw,
+                                                 const bool do_norm, const bool do_rope) {
+  float x[8];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    x[2 * j] = bf2f((bf16_t)(raw[j] & 0xffff));
+    x[2 * j + 1] = bf2f((bf16_t)(raw[j] >> 16));
+  }
+  float ss = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ss += x[j] * x[j];
+  ss += __shfl_xor(ss, 8, 64);
+  ss += __shfl_xor(ss, 4, 64);
+  ss += __shfl_xor(ss, 2, 64);
+  ss += __shfl_xor(ss, 1, 64);
+  const float rs = rsqrtf(ss * (1.0f / 128.0f) + p.eps);
+  u32x4_t wr = (u32x4_t){0u, 0u, 0u, 0u};
+  if (do_norm) {
+    const bf16_t* wsel = which == 0 ? (sc < p.s_txt ? p.wq_txt : p.wq_img) : (sc < p.s_txt ? p.wk_txt : p.wk_img);
+    wr = *(const u32x4_t*)(wsel + sub * 8);
+  }
+  f32x4_t c4 = (f32x4_t){1.f, 1.f, 1.f, 1.f}, s4 = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  if (do_rope) {
+    c4 = *(const f32x4_t*)(p.cosT + (long long)sc * 64 + sub * 4);
+    s4 = *(const f32x4_t*)(p.sinT + (long long)sc * 64 + sub * 4);
+  }
+  u32x4_t o;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    // diffusers RMSNorm: (x * rsqrt(var+eps)).to(bf16) * weight(bf16) -> bf16
+    float a0 = x[2 * j], a1 = x[2 * j + 1];
+    if (do_norm) {
+      a0 = rbf(rbf(a0 * rs) * bf2f((bf16_t)(wr[j] & 0xffff)));
+      a1 = rbf(rbf(a1 * rs) * bf2f((bf16_t)(wr[j] >> 16)));
+    }
+    // apply_rotary_emb (use_real, unbind_dim=-1): out = x*cos + rot(x)*sin in fp32
+    const float r0 = a0 * c4[j] - a1 * s4[j];
+    const float r1 = a1 * c4[j] + a0 * s4[j];
+    o[j] = pack2bf(r0, r1);
+  }
+  return o;
+}
+
 // ---- device code the three attention kernels share ----
 // Per-head RMSNorm(128) + interleaved RoPE of one query row's share of a lane — raw[ks] = the row's elements d = 16 ks + 8 hh + 0..7, lane ^ 32
 // holds the other 64; RoPE pairs (2j, 2j+1) never straddle lanes — with the rounding points of the separate pass (qk_norm_rope_vt_kernel):

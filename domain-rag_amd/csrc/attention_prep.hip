@@ -27,44 +27,7 @@ __global__ __launch_bounds__(256) void qk_norm_rope_vt_kernel(PrepArgs p) {
       const int sc = ok ? s : p.S - 1;
       bf16_t* ptr = base + (long long)sc * p.ld + which * HD + h * 128 + sub * 8;
       const u32x4_t raw = *(const u32x4_t*)ptr;
-      float x[8];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        x[2 * j] = bf2f((bf16_t)(raw[j] & 0xffff));
-        x[2 * j + 1] = bf2f((bf16_t)(raw[j] >> 16));
-      }
-      float ss = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) ss += x[j] * x[j];
-      ss += __shfl_xor(ss, 8, 64);
-      ss += __shfl_xor(ss, 4, 64);
-      ss += __shfl_xor(ss, 2, 64);
-      ss += __shfl_xor(ss, 1, 64);
-      const float rs = rsqrtf(ss * (1.0f / 128.0f) + p.eps);
-      u32x4_t wr = (u32x4_t){0u, 0u, 0u, 0u};
-      if (do_norm) {
-        const bf16_t* wsel = which == 0 ? (sc < p.s_txt ? p.wq_txt : p.wq_img) : (sc < p.s_txt ? p.wk_txt : p.wk_img);
-        wr = *(const u32x4_t*)(wsel + sub * 8);
-      }
-      f32x4_t c4 = (f32x4_t){1.f, 1.f, 1.f, 1.f}, s4 = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-      if (do_rope) {
-        c4 = *(const f32x4_t*)(p.cosT + (long long)sc * 64 + sub * 4);
-        s4 = *(const f32x4_t*)(p.sinT + (long long)sc * 64 + sub * 4);
-      }
-      u32x4_t o;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        // diffusers RMSNorm: (x * rsqrt(var+eps)).to(bf16) * weight(bf16) -> bf16
-        float a0 = x[2 * j], a1 = x[2 * j + 1];
-        if (do_norm) {
-          a0 = rbf(rbf(a0 * rs) * bf2f((bf16_t)(wr[j] & 0xffff)));
-          a1 = rbf(rbf(a1 * rs) * bf2f((bf16_t)(wr[j] >> 16)));
-        }
-        // apply_rotary_emb (use_real, unbind_dim=-1): out = x*cos + rot(x)*sin in fp32
-        const float r0 = a0 * c4[j] - a1 * s4[j];
-        const float r1 = a1 * c4[j] + a0 * s4[j];
-        o[j] = pack2bf(r0, r1);
-      }
+      const u32x4_t o = qk_norm_rope8(p, which, sc, sub, raw, do_norm, do_rope);
       if (ok) *(u32x4_t*)ptr = o;
     }
   }

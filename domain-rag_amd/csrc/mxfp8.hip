@@ -7,19 +7,9 @@
 // 1.75 — clamped to [-127, 127]; an all-zero block stores byte 127; elements are x * 2^-e rounded to nearest-even to e4m3fn, saturated at
 // +-448 (reachable only under a clamped e).  Non-finite inputs are outside the contract.
 #include "gemm_bf16_kernels.h"
+#include "mx_quant.h"
 
 namespace drag_mx {
-
-// |v| <= 448 as float32 bits (sign cleared) -> the 7 magnitude bits of e4m3fn, round to nearest even
-__device__ __forceinline__ uint32_t e4m3_mag(float a) {
-  const uint32_t b = __float_as_uint(a);
-  if (a >= 0.015625f) {                                   // normal e4m3 (>= 2^-6): round the mantissa to 3 bits; a carry moves the exponent
-    const uint32_t r = (b + 0x7FFFFu + ((b >> 20) & 1u)) >> 20;
-    return r - (120u << 3);                               // exponent bias 127 -> 7
-  }
-  // subnormal: multiples of 2^-9; the sum with 2^23 rounds to nearest even and leaves the integer 0..8 in the low bits (8 = 2^-6)
-  return __float_as_uint(a * 512.0f + 8388608.0f) & 0xFFu;
-}
 
 __global__ __launch_bounds__(256) void quantize_mxfp8_kernel(const bf16_t* __restrict__ x, long long rows, int K, drag_gemm::RowMap xm,
                                                              uint8_t* __restrict__ q, uint8_t* __restrict__ scales) {
@@ -33,31 +23,9 @@ __global__ __launch_bounds__(256) void quantize_mxfp8_kernel(const bf16_t* __res
   const int bt = (int)(row / xm.rpb);
   const long long xoff = (long long)bt * xm.bs + (row - (long long)bt * xm.rpb) * xm.ld + ch * 8;
   const u32x4_t v = *(const u32x4_t*)(x + xoff);
-  // bf16 magnitudes order like their bit patterns
-  uint32_t amax = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    amax = max(amax, v[i] & 0x7FFFu);
-    amax = max(amax, (v[i] >> 16) & 0x7FFFu);
-  }
-  amax = max(amax, (uint32_t)__shfl_xor((int)amax, 1, 64));
-  amax = max(amax, (uint32_t)__shfl_xor((int)amax, 2, 64));
-  int e = (int)(amax >> 7) - 127 - 8 + ((amax & 0x7Fu) > 0x60u ? 1 : 0);     // (a subnormal amax reads E = -127: clamped either way)
-  e = max(e, -127);                                       // bf16's largest exponent gives e = 120: the upper clamp is never reached
-  if (amax == 0) e = 0;
-  const float inv = __uint_as_float((uint32_t)(127 - e) << 23);              // 2^-e, exponent field 7 .. 254
-  u32x2_t o = {0u, 0u};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const uint32_t h = (v[i >> 1] >> ((i & 1) * 16)) & 0xFFFFu;
-    const float a = fminf(__uint_as_float((h & 0x7FFFu) << 16) * inv, 448.0f);
-    const uint32_t byte = ((h >> 8) & 0x80u) | e4m3_mag(a);
-    o[i >> 2] |= byte << ((i & 3) * 8);
-  }
-  // the four scale bytes of this 16-lane group's 128 columns, gathered into its first lane
-  uint32_t s = (uint32_t)(e + 127);
-  s |= (uint32_t)__shfl_down((int)s, 4, 64) << 8;
-  s |= (uint32_t)__shfl_down((int)s, 8, 64) << 16;
+  u32x2_t o;
+  uint32_t s;
+  quantize8(v, o, s);                                      // mx_quant.h: the rule, shared with the attention prep pass
   if (!live) return;
   *(u32x2_t*)(q + row * K + ch * 8) = o;
   if ((threadIdx.x & 15) == 0) *(uint32_t*)(scales + row * (K >> 5) + (ch >> 2)) = s;

@@ -186,12 +186,14 @@ class Engine:
     """Everything stage 2 / stage 3 need, loaded once."""
 
     def __init__(self, kind: str, model_root: str = "./model", synthetic: bool = False, tiny: bool = False, device="cuda",
-                 seed: int = 0, text_encoder: str = "transformers", linear_precision: str | None = None, step_cache: float | None = None,
+                 seed: int = 0, text_encoder: str = "transformers", linear_precision: str | None = None, attention_precision: str | None = None,
+                 step_cache: float | None = None,
                  step_cache_scope: str | None = None, step_cache_order: int | None = None, step_cache_max_run: int | None = None,
                  step_cache_warmup: int | None = None):
         """``text_encoder``: what encodes a prompt-cache miss — "transformers" (the reference's modules, eager torch) or "hip"
         (:mod:`.textenc`; with ``synthetic``: seeded encoders and stand-in tokenizers, results kept in memory).
         ``linear_precision``: the DiT blocks' Linears, "bf16" or "mxfp8" (None: $DRAG_LINEAR_PRECISION, else bf16; :mod:`.flux`).
+        ``attention_precision``: the DiT blocks' attention, "bf16" or "mxfp8" (None: $DRAG_ATTENTION_PRECISION, else bf16; :mod:`.flux`).
         ``step_cache``: threshold of the first-block step cache of the denoise loop (:class:`.step_cache.StepCache`; None: $DRAG_STEP_CACHE, else
         off; 0: off) — the pipeline's ``step_cache`` attribute; ``step_cache_scope``: who decides a reuse, "batch" (the whole batch) or
         "image" (every image for itself; None: $DRAG_STEP_CACHE_SCOPE, else "batch") — the pipeline's ``step_cache_scope``;
@@ -223,7 +225,7 @@ class Engine:
             vp = load_safetensors_dir(os.path.join(flux_dir, "vae"))
             vitp = vit_mod.siglip_to_generic(load_safetensors_dir(os.path.join(redux_dir, "image_encoder")), vitcfg)
             rp = load_safetensors_dir(os.path.join(redux_dir, "image_embedder"))
-        tr = FluxTransformerHIP(cfg, tp, dev, linear_precision=linear_precision)
+        tr = FluxTransformerHIP(cfg, tp, dev, linear_precision=linear_precision, attention_precision=attention_precision)
         vae = vae_mod.FluxVaeHIP(vcfg, vp, dev)
         del tp, vp
         self.cfg, self.vit_cfg = cfg, vitcfg

@@ -41,6 +41,13 @@ LINEAR_PRECISIONS = ("bf16", "mxfp8")
 _LINEAR_PRECISION = os.environ.get("DRAG_LINEAR_PRECISION", "") or "bf16"
 if _LINEAR_PRECISION not in LINEAR_PRECISIONS:
     raise ValueError(f"DRAG_LINEAR_PRECISION must be one of {LINEAR_PRECISIONS}, not {_LINEAR_PRECISION!r}")
+# the precision of the blocks' attention: "bf16" (default) or "mxfp8" (opt-in: ops.qkv_prep_mxfp8 + ops.attention_mxfp8, e4m3 operands for
+# both products; the format and its cost in accuracy: mx.py).  Independent of the Linears' mode.  $DRAG_ATTENTION_PRECISION sets the process
+# default, read once
+ATTENTION_PRECISIONS = ("bf16", "mxfp8")
+_ATTENTION_PRECISION = os.environ.get("DRAG_ATTENTION_PRECISION", "") or "bf16"
+if _ATTENTION_PRECISION not in ATTENTION_PRECISIONS:
+    raise ValueError(f"DRAG_ATTENTION_PRECISION must be one of {ATTENTION_PRECISIONS}, not {_ATTENTION_PRECISION!r}")
 # Linear shapes (N, K) that stay on bf16 INSIDE "mxfp8" mode: those whose MX route, the quantise pass of the activations included, was
 # not faster than drag_gemm_bf16 in the interleaved same-process A/B of scripts/bench_gemm_mxfp8.py at the headline's 42 696 rows
 # (profiles/mxfp8_gemm_ab.log).  A shape that was not measured moves.  With the 128x128 MX kernel (800-890 TFLOP/s against 1348-1434 of
@@ -69,9 +76,11 @@ def latent_image_ids(h: int, w: int) -> torch.Tensor:
 
 
 class FluxTransformerHIP:
-    def __init__(self, cfg: FluxConfig, params: dict, device="cuda", linear_precision: str | None = None):
+    def __init__(self, cfg: FluxConfig, params: dict, device="cuda", linear_precision: str | None = None,
+                 attention_precision: str | None = None):
         """``linear_precision``: "bf16" | "mxfp8" (None: $DRAG_LINEAR_PRECISION, else "bf16") — also a settable attribute; the bf16
-        weights are kept in either mode, so one process can A/B"""
+        weights are kept in either mode, so one process can A/B.  ``attention_precision``: the same for the blocks' attention (None:
+        $DRAG_ATTENTION_PRECISION, else "bf16"), also settable; the two modes are independent"""
         if cfg.attention_head_dim != 128:
             raise ValueError("the HIP attention kernel is specialised for head_dim 128 (all FLUX.1 models)")
         self.cfg = cfg
@@ -145,6 +154,7 @@ class FluxTransformerHIP:
         self._rope_key = None
         self._mx_ready = False
         self.linear_precision = linear_precision or _LINEAR_PRECISION
+        self.attention_precision = attention_precision or _ATTENTION_PRECISION
 
     # ------------------------------------------------------------------ MXFP8 mode
     # What moves (blocks only): both streams' to_q|k|v, the attention out-projections, ff up (+GELU) and ff down, the single blocks'
@@ -173,6 +183,39 @@ class FluxTransformerHIP:
                             blk[k + "@mx"] = ops.quantize_mxfp8(blk[k])
             self._mx_ready = True
         self._linear_precision = value
+
+    @property
+    def attention_precision(self) -> str:
+        return self._attention_precision
+
+    @attention_precision.setter
+    def attention_precision(self, value: str) -> None:
+        if value not in ATTENTION_PRECISIONS:
+            raise ValueError(f"attention_precision must be one of {ATTENTION_PRECISIONS}, not {value!r}")
+        self._attention_precision = value
+
+    @property
+    def _precision_key(self) -> tuple:
+        """what the launch sequence of a forward depends on besides the shapes: the graph key and the step cache hold it"""
+        return (self._linear_precision, self._attention_precision)
+
+    def _attention(self, ws, nb, S, St, wq_txt, wk_txt, wq_img, wk_img, cos, sin, out, ld_o, scale):
+        """one block's attention over ws["qkv"] into ``out`` (rows of ``ld_o``).  "mxfp8": the MX prep pass (qkv stays as projected) and the
+        MX kernel on the workspace's images (_SEPARATE_QPREP is a switch of the bf16 route and is ignored); a shape that kernel refuses
+        by contract takes the bf16 launches, and the launch record shows them.  "bf16": k prepared in place + V^T, q on the kernel's load."""
+        cfg = self.cfg
+        D, H = cfg.dim, cfg.num_attention_heads
+        qkv, vt = ws["qkv"], ws["vt"]
+        if self._attention_precision == "mxfp8" and ops.attention_mxfp8_supported(nb, S, H):
+            ops.qkv_prep_mxfp8(qkv, ws["mxa"], wq_txt, wk_txt, wq_img, wk_img, cos, sin, nb, S, H, 3 * D, St)
+            ops.attention_mxfp8(ws["mxa"], out, nb, S, H, ld_o, S * ld_o, scale)
+        elif _SEPARATE_QPREP:     # A/B switch: the round-1 route (q prepared by the pass, plain attention)
+            ops.qk_norm_rope_vt(qkv, vt, wq_txt, wk_txt, wq_img, wk_img, cos, sin, nb, S, H, 3 * D, St)
+            ops.attention(qkv, qkv.view(-1)[D:], vt, out, nb, S, H, 3 * D, S * 3 * D, ld_o, S * ld_o, scale)
+        else:
+            # k: RMSNorm + RoPE in place, V -> V^T; q: norm_q / norm_added_q + RoPE inside the attention kernel's Q load
+            ops.k_norm_rope_vt(qkv, vt, wk_txt, wk_img, cos, sin, nb, S, H, 3 * D, St)
+            ops.attention_qprep(qkv, qkv.view(-1)[D:], vt, out, nb, S, H, 3 * D, S * 3 * D, ld_o, S * ld_o, scale, wq_txt, wq_img, cos, sin, St)
 
     def _mx_moves(self, N: int, K: int) -> bool:
         return self._linear_precision == "mxfp8" and (N, K) not in _MX_STAYS_BF16 and K % 128 == 0 and N % 8 == 0
@@ -294,14 +337,7 @@ class FluxTransformerHIP:
                                          c_batch_stride=S * 3 * D, ldc=3 * D),
                    "cwqkv", dict(a=nrm_txt, out=qkv, bias=blk["cbqkv"], M=Mt, lda=D, c_rows_per_batch=St,
                                  c_batch_stride=S * 3 * D, ldc=3 * D))
-        if _SEPARATE_QPREP:     # A/B switch: the round-1 route (q prepared by the pass, plain attention)
-            ops.qk_norm_rope_vt(qkv, vt, blk["cnq"], blk["cnk"], blk["nq"], blk["nk"], cos, sin, nb, S, H, 3 * D, St)
-            ops.attention(qkv, qkv.view(-1)[D:], vt, attn, nb, S, H, 3 * D, S * 3 * D, D, S * D, scale)
-        else:
-            # k: RMSNorm + RoPE in place, V -> V^T; q: norm_q / norm_added_q + RoPE inside the attention kernel's Q load
-            ops.k_norm_rope_vt(qkv, vt, blk["cnk"], blk["nk"], cos, sin, nb, S, H, 3 * D, St)
-            ops.attention_qprep(qkv, qkv.view(-1)[D:], vt, attn, nb, S, H, 3 * D, S * 3 * D, D, S * D, scale,
-                                blk["cnq"], blk["nq"], cos, sin, St)
+        self._attention(ws, nb, S, St, blk["cnq"], blk["cnk"], blk["nq"], blk["nk"], cos, sin, attn, D, scale)
         self._pair(ws, blk, "wo", dict(a=attn_img, out=x_img, bias=blk["bo"], M=Mi, a_rows_per_batch=Si, a_batch_stride=S * D,
                                        lda=D, c_rows_per_batch=Si, c_batch_stride=S * D, ldc=D, gate=modv[mo + 2 * D:], resid=x_img, ldg=LM),
                    "cwo", dict(a=attn, out=x, bias=blk["cbo"], M=Mt, a_rows_per_batch=St, a_batch_stride=S * D,
@@ -355,13 +391,7 @@ class FluxTransformerHIP:
             else:       # (test-sized widths whose q|k|v block does not end on a tile boundary)
                 ops.gemm(nrm, blk["wqkvm"][: 3 * D], out=qkv, bias=blk["bqkvm"][: 3 * D], M=M, lda=D, ldc=3 * D)
                 ops.gemm(nrm, blk["wqkvm"][3 * D:], out=cat_mlp, bias=blk["bqkvm"][3 * D:], act=ops.ACT_GELU_TANH, M=M, lda=D, ldc=D + F)
-            if _SEPARATE_QPREP:
-                ops.qk_norm_rope_vt(qkv, vt, blk["nq"], blk["nk"], blk["nq"], blk["nk"], cos, sin, nb, S, H, 3 * D, 0)
-                ops.attention(qkv, qkv.view(-1)[D:], vt, catb, nb, S, H, 3 * D, S * 3 * D, D + F, S * (D + F), scale)
-            else:
-                ops.k_norm_rope_vt(qkv, vt, blk["nk"], blk["nk"], cos, sin, nb, S, H, 3 * D, 0)
-                ops.attention_qprep(qkv, qkv.view(-1)[D:], vt, catb, nb, S, H, 3 * D, S * 3 * D, D + F, S * (D + F), scale,
-                                    blk["nq"], blk["nq"], cos, sin, 0)
+            self._attention(ws, nb, S, 0, blk["nq"], blk["nk"], blk["nq"], blk["nk"], cos, sin, catb, D + F, scale)
             proj = dict(a=catb, out=x, bias=blk["bo"], M=M, lda=D + F, c_rows_per_batch=S, c_batch_stride=S * D,
                         ldc=D, gate=modv[mo + 2 * D:], resid=x, ldg=LM)
             if mx_out:
@@ -392,6 +422,8 @@ class FluxTransformerHIP:
             # the widest Linear input (the single blocks' [attn | mlp], D + F columns) as e4m3 bytes + its e8m0 scales
             ws["mxq"] = torch.empty(B * S * (D + F), dtype=torch.uint8, device=self.device)
             ws["mxs"] = torch.empty(B * S * (D + F) // 32, dtype=torch.uint8, device=self.device)
+        if "mxa" not in ws and self._attention_precision == "mxfp8":
+            ws["mxa"] = ops.attention_mxfp8_images(B, S, cfg.num_attention_heads, self.device)      # the six MXFP8 attention images
         cos, sin = self._rope(txt_ids, img_ids)
         hidden = hidden.contiguous(); enc = enc.contiguous(); pooled = pooled.contiguous()
         Mi, Mt = B * Si, B * St
@@ -423,7 +455,7 @@ class FluxTransformerHIP:
         nb = B      # the batch size blocks 1... run at: under a step cache 0 on a reused step, the number of computing images on a mixed one
         if self.double:
             if cache is not None:
-                cache.before_first_block(x, B, St, Si, D, self._linear_precision, self.device)
+                cache.before_first_block(x, B, St, Si, D, self._precision_key, self.device)
             self._double_block(ws, 0, B, St, Si, cos, sin, taps)
             if cache is not None:
                 nb = cache.after_first_block(x, mod, B, St, Si, D, taps, times=times)
@@ -449,15 +481,15 @@ class FluxTransformerHIP:
         A captured graph bakes in the addresses of everything the forward touched, so a cache entry OWNS its workspace,
         RoPE tables and time buffers (they must not be freed or reused while the graph lives), is keyed on the input
         addresses, the shapes AND the RoPE table identity (the same token count can be a different h x w), and the
-        cache is a small LRU (image sizes vary from sample to sample in stage 3).  The Linear precision is part of the key: the two modes
-        are different launch sequences.  A step cache cannot be replayed: its decision needs the host between two pieces of the forward."""
+        cache is a small LRU (image sizes vary from sample to sample in stage 3).  The Linear and the attention precision are part of the key: each
+        combination is a different launch sequence.  A step cache cannot be replayed: its decision needs the host between two pieces of the forward."""
         if cache is not None:
             raise ValueError("forward_graphed takes no step cache (the decision needs the host): call forward(..., cache=...)")
         t = torch.as_tensor(timestep, dtype=torch.float32).cpu().reshape(-1)
         g = None if guidance is None else torch.as_tensor(guidance, dtype=torch.float32).cpu().reshape(-1)
         rope_key = self._ids_key(txt_ids, img_ids)
         key = (hidden.data_ptr(), enc.data_ptr(), pooled.data_ptr(), tuple(hidden.shape), tuple(enc.shape), tuple(pooled.shape),
-               guidance is None, rope_key, self._linear_precision)
+               guidance is None, rope_key) + self._precision_key
         graphs = self.__dict__.setdefault("_graphs", {})
         ent = graphs.pop(key, None)
         if ent is None:

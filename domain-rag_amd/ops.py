@@ -210,14 +210,15 @@ def _recorded(call, shape, kind=False):
     _recorder.is_conv.append(kind)
 
 
-def _recorded_attention(call, B, S, H, qprep, vrow):
+def _recorded_attention(call, B, S, H, qprep, vrow, mx=False):
     """run one head_dim-128 attention launch, bracketed by events when a recorder is installed (4 S^2 128 flops per batch and head:
     q k^T and p v; the kernel name from the library's own dispatch, ``drag_attention_bf16_kernel_name``)"""
     if _recorder is None:
         call()
         return
     # the name before the launch: what the launch is about to read is what gets reported
-    name = _lib.load().drag_attention_bf16_kernel_name(S, int(vrow), int(qprep)).decode()
+    lib = _lib.load()
+    name = (lib.drag_attention_mxfp8_kernel_name(S) if mx else lib.drag_attention_bf16_kernel_name(S, int(vrow), int(qprep))).decode()
     s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s_ev.record()
     call()
@@ -431,13 +432,18 @@ def _attention_reach(kind: str, B: int, S: int, H: int, ld: int = 0, batch_strid
     """elements, counted from an operand's first one, that the head_dim-128 attention path addresses (one more than the largest offset; pure
     integers, tests/test_attention_room_host.py enumerates the addresses).  ``kind``: "rows" = q, k, row-major v or ``out`` (row s of batch b at
     b * batch_stride + s * ld, head h at + 128 h); "vt" = the V^T image; "prep" = the prep pass's qkv (batch b at b * S * ld, q | k | v side by
-    side in a row); "rope" = one RoPE table (f32); "norm" = one RMSNorm weight"""
+    side in a row); "rope" = one RoPE table (f32); "norm" = one RMSNorm weight; the dense MXFP8 images (bytes, s_pad = S rounded up to 128):
+    "mx_rows" = q or k elements [B, H, s_pad, 128], "mx_row_scales" = their scales [B, H, s_pad, 4], "mx_vt" = V^T elements [B, H, 128, s_pad],
+    "mx_vt_scales" = its scales [B, H, 128, s_pad / 32]"""
     if kind == "rows":
         return (B - 1) * batch_stride + (S - 1) * ld + H * 128
     if kind == "vt":
         return B * H * 128 * ((S + 63) // 64 * 64)
     if kind == "prep":
         return (B * S - 1) * ld + 3 * H * 128
+    if kind in ("mx_rows", "mx_row_scales", "mx_vt", "mx_vt_scales"):
+        s_pad = (S + 127) // 128 * 128                     # the MXFP8 images' padding: S rounded up to a whole 128-key tile
+        return B * H * {"mx_rows": s_pad * 128, "mx_row_scales": s_pad * 4, "mx_vt": 128 * s_pad, "mx_vt_scales": 128 * (s_pad // 32)}[kind]
     if kind == "rope":
         return S * 64
     if kind == "norm":
@@ -445,12 +451,21 @@ def _attention_reach(kind: str, B: int, S: int, H: int, ld: int = 0, batch_strid
     raise KeyError(kind)
 
 
-def _attention_room(what: str, B: int, S: int, H: int, rows=(), vt=None, prep=None, ropes=(), norms=()) -> None:
+_MX_IMAGE_KINDS = ("mx_rows", "mx_row_scales", "mx_rows", "mx_row_scales", "mx_vt", "mx_vt_scales")      # (qq, qs, kq, ks, vq, vs)
+
+
+def _attention_room(what: str, B: int, S: int, H: int, rows=(), vt=None, prep=None, ropes=(), norms=(), mx=None) -> None:
     """the operands of one of the five head_dim-128 attention wrappers before the launch: every optional one a GPU tensor of its dtype, no
     negative stride, output rows that do not overlap, and the last element each operand's addressing reaches (``_attention_reach``) inside
     its storage — a wrong stride is an error here, not a memory fault in the kernel (shapes the library refuses — ld % 8, ld_o % 4, the
     2 GiB K span, B / S / H <= 0 — stay the library's to report).  ``rows``: (name, tensor, ld, batch_stride); ``prep``: (tensor, ld);
-    ``ropes`` / ``norms``: (name, tensor or None)"""
+    ``ropes`` / ``norms``: (name, tensor or None); ``mx``: the six MXFP8 images (qq, qs, kq, ks, vq, vs), GPU uint8"""
+    if mx is not None:
+        if len(mx) != 6:
+            raise ValueError(f"{what}.images: the six MXFP8 images (qq, qs, kq, ks, vq, vs) expected, got {len(mx)}")
+        for name, t in zip(("qq", "qs", "kq", "ks", "vq", "vs"), mx):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8):
+                raise ValueError(f"{what}.images.{name}: expected a GPU uint8 tensor, got {getattr(t, 'dtype', type(t))}")
     for group, dtype in ((ropes, torch.float32), (norms, torch.bfloat16)):
         for name, t in group:
             if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype):
@@ -481,6 +496,11 @@ def _attention_room(what: str, B: int, S: int, H: int, rows=(), vt=None, prep=No
         for name, t in group:
             if t is not None and _attention_reach(kind, B, S, H) > _room(t):
                 raise ValueError(f"{what}.{name}: expected at least {_attention_reach(kind, B, S, H)} elements, got {_room(t)} from its start")
+    if mx is not None:
+        for name, t, kind in zip(("qq", "qs", "kq", "ks", "vq", "vs"), mx, _MX_IMAGE_KINDS):
+            if _attention_reach(kind, B, S, H) > _room(t):
+                raise ValueError(f"{what}.images.{name}: the dense image is {_attention_reach(kind, B, S, H)} bytes (s_pad = S rounded up to 128), "
+                                 f"got {_room(t)} from its start")
 
 
 def qk_norm_rope_vt(qkv: torch.Tensor, vt: torch.Tensor, wq_txt, wk_txt, wq_img, wk_img, rope_cos, rope_sin,
@@ -583,6 +603,47 @@ def attention_v(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Te
     _recorded_attention(lambda: check(lib.drag_attention_v_bf16(_p(q), _p(k), _p(v), _p(out), B, S, H, ld_qk, qk_batch_stride, ld_o, o_batch_stride,
                                                                 scale, _p(wq_txt), _p(wq_img), _p(rope_cos), _p(rope_sin), s_txt, eps, _stream()),
                                       "drag_attention_v_bf16"), B, S, H, wq_txt is not None, True)
+
+
+def attention_mxfp8_supported(B: int, S: int, H: int) -> bool:
+    """does the MXFP8 attention path take this shape (``drag_attention_mxfp8_supported``: B, H in 1 .. 65535, S in 1 .. 2^23)?  A pure query:
+    callers that fall back to the bf16 launches (FluxTransformerHIP) ask before they launch."""
+    return bool(_lib.load().drag_attention_mxfp8_supported(B, S, H))
+
+
+def attention_mxfp8_images(B: int, S: int, H: int, device) -> tuple:
+    """uninitialised buffers for the six MXFP8 attention images (qq, qs, kq, ks, vq, vs) of ``qkv_prep_mxfp8`` / ``attention_mxfp8``:
+    uint8 [B, H, s_pad, 128], [B, H, s_pad, 4], the same two for k, [B, H, 128, s_pad], [B, H, 128, s_pad / 32]; s_pad = S rounded up to 128"""
+    sp = (S + 127) // 128 * 128
+    shapes = ((sp, 128), (sp, 4), (sp, 128), (sp, 4), (128, sp), (128, sp // 32))
+    return tuple(torch.empty((B, H) + shp, dtype=torch.uint8, device=device) for shp in shapes)
+
+
+def qkv_prep_mxfp8(qkv: torch.Tensor, images, wq_txt, wk_txt, wq_img, wk_img, rope_cos, rope_sin, B: int, S: int, H: int, ld: int,
+                   s_txt: int, eps: float = 1e-6) -> None:
+    """The pass in front of ``attention_mxfp8`` (``drag_qkv_prep_mxfp8``): reads ``qkv`` under ``qk_norm_rope_vt``'s layout contract and leaves it
+    UNTOUCHED; writes every byte of the six dense images ``images`` = (qq, qs, kq, ks, vq, vs) (``attention_mxfp8_images``; format:
+    :mod:`.mx`): q and k are the values ``qk_norm_rope_vt`` would store, quantised along head_dim; V^T is quantised along the keys in natural
+    key order, keys >= S as zeros; q / k rows >= S are zero bytes under scale byte 127."""
+    lib = _lib.load()
+    _need(qkv, torch.bfloat16, "qkv")
+    _attention_room("qkv_prep_mxfp8", B, S, H, prep=(qkv, ld), ropes=(("rope_cos", rope_cos), ("rope_sin", rope_sin)),
+                    norms=(("wq_txt", wq_txt), ("wk_txt", wk_txt), ("wq_img", wq_img), ("wk_img", wk_img)), mx=images)
+    check(lib.drag_qkv_prep_mxfp8(_p(qkv), _p(wq_txt), _p(wk_txt), _p(wq_img), _p(wk_img), _p(rope_cos), _p(rope_sin), B, S, H, ld, s_txt, eps,
+                                  *[_p(t) for t in images], _stream()), "drag_qkv_prep_mxfp8")
+
+
+def attention_mxfp8(images, out: torch.Tensor, B: int, S: int, H: int, ld_o: int, o_batch_stride: int, scale: float) -> None:
+    """head_dim-128 attention over the MXFP8 images of ``qkv_prep_mxfp8`` (``drag_attention_mxfp8``; e4m3 operands on the block-scaled matrix
+    instruction for both products, float32 softmax).  ``out`` under ``attention``'s contract (token s of batch b at b * o_batch_stride +
+    s * ld_o, 8-byte aligned, ``ld_o`` >= H*128 and a multiple of 4; only the B * S * H*128 owned elements are written).  Short images, a
+    negative stride or overlapping output rows raise ValueError before anything is launched; a shape the kernel does not take
+    (``attention_mxfp8_supported``) or a non-positive ``scale`` is the library's error."""
+    lib = _lib.load()
+    _need(out, torch.bfloat16, "out")
+    _attention_room("attention_mxfp8", B, S, H, rows=(("out", out, ld_o, o_batch_stride),), mx=images)
+    _recorded_attention(lambda: check(lib.drag_attention_mxfp8(*[_p(t) for t in images], _p(out), B, S, H, ld_o, o_batch_stride, scale, _stream()),
+                                      "drag_attention_mxfp8"), B, S, H, False, False, mx=True)
 
 
 def layernorm(x: torch.Tensor, y: torch.Tensor, M: int, D: int, *, scale=None, shift=None, gamma=None, beta=None,

@@ -152,7 +152,7 @@ class StepCache:
     computed step), R (the residual of that step's remaining blocks, image rows only: the final projection reads nothing else) — with order
     1 a fourth, P, and per image ``t_last``, ``t_prev`` (host floats) and ``has_prev``; the float64 ratios and the reduction workspace.
     Validity is per image (``valid_images``; ``valid``: all of them): every image is invalid, and has no P, after ``reset()``, after a
-    change of (B, Si, D) and after a change of the model's ``linear_precision``.  Reading the ratios back is the one host synchronisation
+    change of (B, Si, D) and after a change of the model's ``linear_precision`` or ``attention_precision``.  Reading the ratios back is the one host synchronisation
     per step."""
 
     def __init__(self, threshold: float, forced: Sequence[bool] | None = None, scope: str = "batch",

@@ -275,6 +275,37 @@ int drag_attention_bf16_choice(int32_t S, int32_t v_row_major, int32_t q_prep);
  * q preparation only).  What the NEXT launch of that shape takes under the current switches: ask before the launch.  A pure query. */
 const char* drag_attention_bf16_kernel_name(int32_t S, int32_t v_row_major, int32_t q_prep);
 
+/* ---------------------------------------------------------------------------------------
+ * MXFP8 attention (opt-in: FluxTransformerHIP(attention_precision="mxfp8"); the default path is bf16 and calls none of these).
+ * Operands, per (batch, head), all dense, blocks by the rule of drag_quantize_mxfp8 (domain-rag_amd/mx.py states it):
+ *   q, k : e4m3fn bytes [B, H, s_pad, 128] + e8m0 bytes [B, H, s_pad, 4]: the values drag_qk_norm_rope_vt_bf16 would write (RMSNorm and RoPE,
+ *          rounded to bf16), quantised along head_dim.  s_pad = S rounded up to a multiple of 128 (drag_attention_mxfp8_s_pad); rows
+ *          >= S hold zero bytes and scale byte 127.
+ *   V^T  : e4m3fn bytes [B, H, 128, s_pad] + e8m0 bytes [B, H, 128, s_pad / 32]: quantised along the key axis in blocks of the 32 keys
+ *          [32 j, 32 j + 32), keys >= S as zeros, keys in NATURAL order inside a block (the kernel computes its scores in the order its P
+ *          registers need, so the image needs no permutation).
+ *   P    : p = exp(s - m), m the running row maximum (p <= 1); the matrix operand is e4m3(p * 2^8) under the constant scale byte 119
+ *          (2^-8); the row sum adds the float32 p before that rounding; accumulators, rescales and 1 / l are float32.
+ *   Scores are (q^ . k^) * scale in float32 (the scale is not folded into q); keys >= S are masked to -inf (a zero k row scores 0).
+ *
+ * drag_qkv_prep_mxfp8 — reads qkv under drag_qk_norm_rope_vt_bf16's layout contract (ld, s_txt, the four norm weights all-or-none, the
+ * RoPE tables both-or-neither; batch b at b * S * ld), leaves it untouched, and writes every byte of the six images, padding included.
+ * qkv and the element images 16-byte aligned, the scale images 4-byte aligned.
+ * drag_attention_mxfp8 — flash attention over those images on v_mfma_scale_f32_16x16x128_f8f6f4 (both products), head_dim 128.  out under
+ * drag_attention_bf16's contract: token s of batch b at b * o_batch_stride + s * ld_o, head h at + 128 h, 8-byte aligned, ld_o % 4 == 0,
+ * ld_o >= H * 128, o_batch_stride % 4 == 0; only the B * S * H*128 owned elements are written.
+ * Both refuse, before any launch, B or H outside 1 .. 65535 and S outside 1 .. 2^23 (drag_attention_mxfp8_supported: the same test as a
+ * pure query) and misaligned operands.  drag_attention_mxfp8_kernel_name: the kernel the next launch over S keys takes, as a profiler
+ * prints it (a pure query).  Nothing in the reference corresponds (its attention is bf16 SDPA). */
+int drag_qkv_prep_mxfp8(const void* qkv, const void* wq_txt, const void* wk_txt, const void* wq_img, const void* wk_img,
+                        const float* rope_cos, const float* rope_sin, int32_t B, int32_t S, int32_t H, int32_t ld, int32_t s_txt,
+                        float eps, void* qq, void* qs, void* kq, void* ks, void* vq, void* vs, void* stream);
+int drag_attention_mxfp8(const void* qq, const void* qs, const void* kq, const void* ks, const void* vq, const void* vs, void* out,
+                         int32_t B, int32_t S, int32_t H, int32_t ld_o, int64_t o_batch_stride, float scale, void* stream);
+int drag_attention_mxfp8_s_pad(int32_t S);
+int drag_attention_mxfp8_supported(int32_t B, int32_t S, int32_t H);
+const char* drag_attention_mxfp8_kernel_name(int32_t S);
+
 /* drag_layernorm_modulate_bf16 — y = LN(x) * (1 + scale[b]) + shift[b]   (no affine LN, eps given)
  * or, with gamma/beta != NULL, y = LN(x) * gamma + beta (affine LayerNorm, scale/shift NULL: both pairs at once are refused),
  * or, with all four NULL, y = LN(x).

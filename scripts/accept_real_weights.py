@@ -271,6 +271,8 @@ def _hip_pipes(args, kind, encoders):
         pipe.pipe.step_cache_order = getattr(args, "step_cache_order", None) or 0
         pipe.pipe.step_cache_max_run = getattr(args, "step_cache_max_run", None) or 0
         pipe.pipe.step_cache_warmup = getattr(args, "step_cache_warmup", None) or 0
+    if getattr(args, "attention_precision", None):      # --attention-precision: the HIP side's DiT attention (flux.FluxTransformerHIP)
+        pipe.pipe.tr.attention_precision = args.attention_precision
     return prior, pipe
 
 
@@ -368,6 +370,8 @@ def main(argv=None) -> int:
                     help="with --step-cache: after N reused steps in a row the next one computes (default: 0, no limit)")
     ap.add_argument("--step-cache-warmup", type=int, default=0, metavar="N",
                     help="with --step-cache: the first N steps compute (default: 0)")
+    ap.add_argument("--attention-precision", choices=["bf16", "mxfp8"], default=None,
+                    help="run the HIP stage-2 / stage-3 pipelines with this attention precision in the DiT (default: the process default, bf16)")
     args = ap.parse_args(argv)
     sections = [s for s in args.sections.split(",") if s]
     bad = [s for s in sections if s not in SECTIONS]
@@ -385,6 +389,8 @@ def main(argv=None) -> int:
         for name in ("step_cache_max_run", "step_cache_warmup"):
             if getattr(args, name) > 0:
                 report[name] = getattr(args, name)
+    if args.attention_precision == "mxfp8":
+        report["attention_precision"] = args.attention_precision
     if any(s in sections for s in ("stage2", "stage3")) and not args.target:
         report["missing"].append("--target <inpainted k-shot image>")
     if report["missing"]:
