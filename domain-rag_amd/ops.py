@@ -149,8 +149,55 @@ def _need(t: torch.Tensor, dtype, name: str):
         raise TypeError(f"{name}: expected {dtype}, got {t.dtype}")
 
 
-def _gemm_args(a, w, out, bias, act, act_n0, gate, resid, out_f32, M, a_rows_per_batch, a_batch_stride, lda, c_rows_per_batch,
-               c_batch_stride, ldc, ldg, out2, ldc2, n_split):
+def _room(t: torch.Tensor) -> int:
+    """elements of ``t``'s storage from its first element on"""
+    return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+
+
+def _batches(M: int, rows_per_batch: int) -> int:
+    """batches that the M rows of a batched-row map fall into (``_rows_reach``)"""
+    return -(-M // rows_per_batch) if 0 < rows_per_batch < M else 1
+
+
+def _rows_reach(M: int, cols: int, ld: int, rows_per_batch: int = 0, batch_stride: int = 0) -> int:
+    """elements, counted from an operand's first one, that M logical rows of ``cols`` elements address under the library's batched-row map
+    (``drag_gemm_bf16``, ``drag_quantize_mxfp8``, ``drag_layernorm_modulate_bf16``): row r at (r // rpb) * batch_stride + (r % rpb) * ld with
+    rpb = ``rows_per_batch`` if 0 < ``rows_per_batch`` < M, else M (one batch).  One more than the largest offset for strides >= 0 (a negative
+    one is the caller's to refuse); pure integers, tests/test_rows_reach_host.py enumerates the addresses."""
+    if M <= 0 or cols <= 0:
+        return 0
+    rpb = rows_per_batch if 0 < rows_per_batch < M else M
+    b, s = divmod(M - 1, rpb)                               # the last row's batch and row in it
+    last = b * batch_stride + s * ld
+    if b > 0:                                               # a short last batch: the full batch before it may reach further
+        last = max(last, (b - 1) * batch_stride + (rpb - 1) * ld)
+    return last + cols
+
+
+def _fit(t: torch.Tensor, reach: int, what: str, *row_map: int) -> None:
+    """the ``reach`` elements that a launch addresses from ``t``'s first one must lie inside its storage: a wrong stride is an error here,
+    not a memory fault in the kernel.  ``row_map``: ``_rows_reach``'s arguments, for the message."""
+    if reach > _room(t):
+        how = f" ({row_map[0]} rows of {row_map[1]}; row stride, rows per batch, batch stride: {row_map[2:]})" if row_map else ""
+        raise ValueError(f"{what}: the launch addresses {reach} elements from its start{how}, the tensor holds {_room(t)}")
+
+
+def _linear_fit(what: str, M: int, N: int, cols: int, out, resid, bias, gate, ldc: int, rows_per_batch: int, batch_stride: int, ldg: int) -> None:
+    """the destination side of a Linear (``gemm``, ``gemm_mxfp8``): ``out`` and ``resid`` hold M rows of ``cols`` under the destination's row
+    map, ``bias`` N elements, ``gate`` one row of N per batch, ``ldg`` apart"""
+    reach = _rows_reach(M, cols, ldc, rows_per_batch, batch_stride)
+    _fit(out, reach, what + ".out", M, cols, ldc, rows_per_batch, batch_stride)
+    if resid is not None:
+        _fit(resid, reach, what + ".resid", M, cols, ldc, rows_per_batch, batch_stride)
+    if bias is not None:
+        _fit(bias, N, what + ".bias")
+    if gate is not None:
+        nb = _batches(M, rows_per_batch)
+        _fit(gate, _rows_reach(nb, N, ldg), what + ".gate", nb, N, ldg)
+
+
+def _gemm_args(a, w, out=None, *, bias=None, act=ACT_NONE, act_n0=0, gate=None, resid=None, out_f32=False, M=None, a_rows_per_batch=0,
+               a_batch_stride=0, lda=None, c_rows_per_batch=0, c_batch_stride=0, ldc=None, ldg=0, out2=None, ldc2=0, n_split=0):
     """(GemmArgs, out, (M, N, K)) of one Linear (argument meaning: ``gemm``)"""
     _need(a, torch.bfloat16, "gemm.a")
     _need(w, torch.bfloat16, "gemm.w")
@@ -171,15 +218,12 @@ def _gemm_args(a, w, out, bias, act, act_n0, gate, resid, out_f32, M, a_rows_per
         # a 2-D destination carries its own row stride (a two-destination launch writes n_split columns into `out`, not N: defaulting to N
         # there wrote past the tensor — round 5, found as a GPU memory fault by a test that forgot ldc)
         ldc = out.stride(-2) if out.dim() >= 2 and out.stride(-1) == 1 else N
-    if c_rows_per_batch == 0 and (out2 is None or (0 < n_split < N and n_split % 256 == 0)):     # (an invalid n_split is the library's to report)
-        # last element written into each destination must lie inside its storage: a wrong ldc is an error here, not a memory fault there
-        def _room(t):
-            return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
-        cols = n_split if out2 is not None else N
-        if (M - 1) * ldc + cols > _room(out):
-            raise ValueError(f"gemm.out: {M} rows of stride {ldc} x {cols} columns do not fit the destination ({_room(out)} elements from its start)")
-        if out2 is not None and (M - 1) * ldc2 + (N - n_split) > _room(out2):
-            raise ValueError(f"gemm.out2: {M} rows of stride {ldc2} x {N - n_split} columns do not fit the destination ({_room(out2)} elements from its start)")
+    _fit(a, _rows_reach(M, K, lda, a_rows_per_batch, a_batch_stride), "gemm.a", M, K, lda, a_rows_per_batch, a_batch_stride)
+    if out2 is None:
+        _linear_fit("gemm", M, N, N, out, resid, bias, gate, ldc, c_rows_per_batch, c_batch_stride, ldg)
+    elif 0 < n_split < N and n_split % 256 == 0:            # (an invalid n_split is the library's to report)
+        _linear_fit("gemm", M, N, n_split, out, resid, bias, gate, ldc, c_rows_per_batch, c_batch_stride, ldg)
+        _fit(out2, _rows_reach(M, N - n_split, ldc2), "gemm.out2", M, N - n_split, ldc2)
     args = GemmArgs()
     args.A, args.W, args.C = a.data_ptr(), w.data_ptr(), out.data_ptr()
     args.bias = bias.data_ptr() if bias is not None else None
@@ -195,35 +239,38 @@ def _gemm_args(a, w, out, bias, act, act_n0, gate, resid, out_f32, M, a_rows_per
     return args, out, (M, N, K)
 
 
-def _recorded(call, shape, kind=False):
-    """run one GEMM launch, bracketed by events when a recorder is installed"""
-    if _recorder is None:
+def _bracketed(call, f32: bool = False):
+    """run ``call``; with a recorder installed (for a float32 launch: one that takes those) between two timing events on the launch stream,
+    and return the pair"""
+    if _recorder is None or (f32 and not _recorder.f32):
         call()
-        return
+        return None
     s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s_ev.record()
     call()
     e_ev.record()
-    M, N, K = shape
-    _recorder.events.append((s_ev, e_ev, 2.0 * M * N * K))
-    _recorder.shapes.append(shape)
-    _recorder.is_conv.append(kind)
+    return s_ev, e_ev
+
+
+def _recorded(call, shape, kind=False):
+    """run one matrix-core launch of 2 M N K flops (``shape``), recorded when a recorder is installed; ``kind``: ``GemmRecorder.kernel_of``"""
+    ev = _bracketed(call, kind == "f32")
+    if ev is not None:
+        M, N, K = shape
+        _recorder.events.append((*ev, 2.0 * M * N * K))
+        _recorder.shapes.append(shape)
+        _recorder.is_conv.append(kind)
 
 
 def _recorded_attention(call, B, S, H, qprep, vrow, mx=False):
-    """run one head_dim-128 attention launch, bracketed by events when a recorder is installed (4 S^2 128 flops per batch and head:
-    q k^T and p v; the kernel name from the library's own dispatch, ``drag_attention_bf16_kernel_name``)"""
-    if _recorder is None:
-        call()
-        return
-    # the name before the launch: what the launch is about to read is what gets reported
-    lib = _lib.load()
-    name = (lib.drag_attention_mxfp8_kernel_name(S) if mx else lib.drag_attention_bf16_kernel_name(S, int(vrow), int(qprep))).decode()
-    s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s_ev.record()
-    call()
-    e_ev.record()
-    _recorder.attn.append((s_ev, e_ev, 4.0 * S * S * 128 * H * B, name))
+    """run one head_dim-128 attention launch, recorded when a recorder is installed (4 S^2 128 flops per batch and head: q k^T and p v;
+    the kernel name from the library's own dispatch, ``drag_attention_bf16_kernel_name``)"""
+    if _recorder is not None:   # the name before the launch: what the launch is about to read is what gets reported
+        lib = _lib.load()
+        name = (lib.drag_attention_mxfp8_kernel_name(S) if mx else lib.drag_attention_bf16_kernel_name(S, int(vrow), int(qprep))).decode()
+    ev = _bracketed(call)
+    if ev is not None:
+        _recorder.attn.append((*ev, 4.0 * S * S * 128 * H * B, name))
 
 
 _gemm_workspaces: dict[int, torch.Tensor] = {}
@@ -255,7 +302,6 @@ def gemm_workspace(device: torch.device, mbytes: int | None = None) -> None:
     $DRAG_GEMM_WORKSPACE_MB (default 64; 0 = none, no launch is split) — a Linear of few output tiles and a long K (batch-1 proj_out /
     ff down-projections) then runs as stacked K slices + one reduce pass.  Not taken during stream capture (the buffer must outlive the
     graph: call this before capturing)."""
-    import os
     idx = device.index if device.index is not None else torch.cuda.current_device()
     if mbytes is None:
         mbytes = int(os.environ.get("DRAG_GEMM_WORKSPACE_MB", "64"))
@@ -291,8 +337,9 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor | None = None, *, b
         gemm_workspace(a.device)
     if a.is_cuda:
         _workspace_guard(a)
-    args, out, shape = _gemm_args(a, w, out, bias, act, act_n0, gate, resid, out_f32, M, a_rows_per_batch, a_batch_stride, lda,
-                                  c_rows_per_batch, c_batch_stride, ldc, ldg, out2, ldc2, n_split)
+    args, out, shape = _gemm_args(a, w, out, bias=bias, act=act, act_n0=act_n0, gate=gate, resid=resid, out_f32=out_f32, M=M,
+                                  a_rows_per_batch=a_rows_per_batch, a_batch_stride=a_batch_stride, lda=lda, c_rows_per_batch=c_rows_per_batch,
+                                  c_batch_stride=c_batch_stride, ldc=ldc, ldg=ldg, out2=out2, ldc2=ldc2, n_split=n_split)
     slices = lib.drag_gemm_bf16_splitk_slices(ctypes.byref(args)) if _recorder is not None else 0
     _recorded(lambda: check(lib.drag_gemm_bf16(ctypes.byref(args), _stream()), "drag_gemm_bf16"), shape, ("splitk", slices) if slices else False)
     return out
@@ -310,19 +357,10 @@ def gemm_pair(first: dict, second: dict):
     alone; bit-identical to ``gemm(**first); gemm(**second)`` either way.  A FluxTransformerBlock's image-stream / text-stream
     pairs (to_q|k|v + add_q|k|v_proj, to_out + to_add_out, ff + ff_context)."""
     lib = _lib.load()
-    packed = []
-    for kw in (first, second):
-        kw = dict(kw)
-        a, w, out = kw.pop("a"), kw.pop("w"), kw.pop("out", None)
-        d = dict(bias=None, act=ACT_NONE, act_n0=0, gate=None, resid=None, out_f32=False, M=None, a_rows_per_batch=0, a_batch_stride=0,
-                 lda=None, c_rows_per_batch=0, c_batch_stride=0, ldc=None, ldg=0)
-        unknown = set(kw) - set(d)
-        if unknown:
-            raise TypeError(f"gemm_pair: unexpected arguments {sorted(unknown)}")
-        d.update(kw)
-        packed.append(_gemm_args(a, w, out, d["bias"], d["act"], d["act_n0"], d["gate"], d["resid"], d["out_f32"], d["M"], d["a_rows_per_batch"],
-                                 d["a_batch_stride"], d["lda"], d["c_rows_per_batch"], d["c_batch_stride"], d["ldc"], d["ldg"], None, 0, 0))
-    (a1, o1, s1), (a2, o2, s2) = packed
+    two_dest = {"out2", "ldc2", "n_split"} & (first.keys() | second.keys())
+    if two_dest:
+        raise TypeError(f"gemm_pair: unexpected arguments {sorted(two_dest)} (a pair has no two-destination form)")
+    (a1, o1, s1), (a2, o2, s2) = _gemm_args(**first), _gemm_args(**second)
     if s1[1:] != s2[1:]:
         raise ValueError(f"gemm_pair: the two problems must share N and K (got {s1} and {s2})")
     if (a1.act, a1.act_n0, a1.out_f32) != (a2.act, a2.act_n0, a2.out_f32):
@@ -364,11 +402,7 @@ def quantize_mxfp8(x: torch.Tensor, *, M: int | None = None, K: int | None = Non
         lda = K
     if K % 128:
         raise ValueError(f"quantize_mxfp8: K = {K} must be a multiple of 128")
-    # the last element read must lie inside x's storage: a wrong row map is an error here, not a memory fault there
-    rpb = rows_per_batch if 0 < rows_per_batch < M else M
-    last = ((M - 1) // rpb) * batch_stride + ((M - 1) % rpb) * lda + K
-    if last > _room(x):
-        raise ValueError(f"quantize_mxfp8.x: {M} rows of this row map end at element {last}, past the source ({_room(x)} elements from its start)")
+    _fit(x, _rows_reach(M, K, lda, rows_per_batch, batch_stride), "quantize_mxfp8.x", M, K, lda, rows_per_batch, batch_stride)
     if out is None:
         q = torch.empty((M, K), dtype=torch.uint8, device=x.device)
         s = torch.empty((M, K // 32), dtype=torch.uint8, device=x.device)
@@ -406,16 +440,10 @@ def gemm_mxfp8(aq: torch.Tensor, ascale: torch.Tensor, wq: torch.Tensor, wscale:
     _need(out, torch.bfloat16, "gemm_mxfp8.out")
     if ldc is None:
         ldc = out.stride(-2) if out.dim() >= 2 and out.stride(-1) == 1 else N
-    # the last element addressed must lie inside each tensor's storage: a wrong row map is an error here, not a memory fault there
-    rpb = c_rows_per_batch if 0 < c_rows_per_batch < M else M
-    last = ((M - 1) // rpb) * c_batch_stride + ((M - 1) % rpb) * ldc + N
-    nb = (M - 1) // rpb + 1
-    for t, name, need in ((out, "out", last), (resid, "resid", last), (bias, "bias", N), (gate, "gate", (nb - 1) * ldg + N)):
-        if t is None:
-            continue
-        _need(t, torch.bfloat16, "gemm_mxfp8." + name)
-        if need > _room(t):
-            raise ValueError(f"gemm_mxfp8.{name}: the launch addresses {need} elements from its start, the tensor holds {_room(t)}")
+    for t, name in ((resid, "resid"), (bias, "bias"), (gate, "gate")):
+        if t is not None:
+            _need(t, torch.bfloat16, "gemm_mxfp8." + name)
+    _linear_fit("gemm_mxfp8", M, N, N, out, resid, bias, gate, ldc, c_rows_per_batch, c_batch_stride, ldg)
     args = GemmMxArgs()
     args.Aq, args.Ascale, args.Wq, args.Wscale, args.C = aq.data_ptr(), ascale.data_ptr(), wq.data_ptr(), wscale.data_ptr(), out.data_ptr()
     args.bias = bias.data_ptr() if bias is not None else None
@@ -436,11 +464,11 @@ def _attention_reach(kind: str, B: int, S: int, H: int, ld: int = 0, batch_strid
     "mx_rows" = q or k elements [B, H, s_pad, 128], "mx_row_scales" = their scales [B, H, s_pad, 4], "mx_vt" = V^T elements [B, H, 128, s_pad],
     "mx_vt_scales" = its scales [B, H, 128, s_pad / 32]"""
     if kind == "rows":
-        return (B - 1) * batch_stride + (S - 1) * ld + H * 128
+        return _rows_reach(B * S, H * 128, ld, S, batch_stride)
     if kind == "vt":
         return B * H * 128 * ((S + 63) // 64 * 64)
     if kind == "prep":
-        return (B * S - 1) * ld + 3 * H * 128
+        return _rows_reach(B * S, 3 * H * 128, ld)
     if kind in ("mx_rows", "mx_row_scales", "mx_vt", "mx_vt_scales"):
         s_pad = (S + 127) // 128 * 128                     # the MXFP8 images' padding: S rounded up to a whole 128-key tile
         return B * H * {"mx_rows": s_pad * 128, "mx_row_scales": s_pad * 4, "mx_vt": 128 * s_pad, "mx_vt_scales": 128 * (s_pad // 32)}[kind]
@@ -478,29 +506,21 @@ def _attention_room(what: str, B: int, S: int, H: int, rows=(), vt=None, prep=No
             raise ValueError(f"{what}.{name}: negative stride (row stride {ld}, batch stride {bs})")
         if name == "out" and ld < H * 128:
             raise ValueError(f"{what}.out: rows of stride {ld} overlap ({H} heads x 128 = {H * 128} elements each)")
-        reach = _attention_reach("rows", B, S, H, ld, bs)
-        if reach > _room(t):
-            raise ValueError(f"{what}.{name}: {B} x {S} rows of {H * 128} (row stride {ld}, batch stride {bs}) reach element {reach} of "
-                             f"{_room(t)} from its start")
-    if vt is not None and _attention_reach("vt", B, S, H) > _room(vt):
-        raise ValueError(f"{what}.vt: [B, H, 128, s_pad] with s_pad = {(S + 63) // 64 * 64} (S rounded up to 64) is "
-                         f"{_attention_reach('vt', B, S, H)} elements, got {_room(vt)} from its start")
+        _fit(t, _attention_reach("rows", B, S, H, ld, bs), f"{what}.{name}", B * S, H * 128, ld, S, bs)
+    if vt is not None:
+        _fit(vt, _attention_reach("vt", B, S, H), what + ".vt (dense [B, H, 128, s_pad], s_pad = S rounded up to 64)")
     if prep is not None:
         t, ld = prep
         if ld < 0:
             raise ValueError(f"{what}.qkv: negative row stride {ld}")
-        if _attention_reach("prep", B, S, H, ld) > _room(t):
-            raise ValueError(f"{what}.qkv: {B * S} rows of stride {ld} (batch b at b * S * ld) reach element "
-                             f"{_attention_reach('prep', B, S, H, ld)} of {_room(t)} from its start")
+        _fit(t, _attention_reach("prep", B, S, H, ld), what + ".qkv", B * S, 3 * H * 128, ld)
     for group, kind in ((ropes, "rope"), (norms, "norm")):
         for name, t in group:
-            if t is not None and _attention_reach(kind, B, S, H) > _room(t):
-                raise ValueError(f"{what}.{name}: expected at least {_attention_reach(kind, B, S, H)} elements, got {_room(t)} from its start")
+            if t is not None:
+                _fit(t, _attention_reach(kind, B, S, H), f"{what}.{name}")
     if mx is not None:
         for name, t, kind in zip(("qq", "qs", "kq", "ks", "vq", "vs"), mx, _MX_IMAGE_KINDS):
-            if _attention_reach(kind, B, S, H) > _room(t):
-                raise ValueError(f"{what}.images.{name}: the dense image is {_attention_reach(kind, B, S, H)} bytes (s_pad = S rounded up to 128), "
-                                 f"got {_room(t)} from its start")
+            _fit(t, _attention_reach(kind, B, S, H), f"{what}.images.{name} (a dense image, s_pad = S rounded up to 128)")
 
 
 def qk_norm_rope_vt(qkv: torch.Tensor, vt: torch.Tensor, wq_txt, wk_txt, wq_img, wk_img, rope_cos, rope_sin,
@@ -678,22 +698,15 @@ def _layernorm_room(x: torch.Tensor, y: torch.Tensor, mods: dict, vecs: dict, M:
     for name, v in (("ldx", ldx), ("ldy", ldy), ("ld_mod", ld_mod), ("x_batch_stride", x_batch_stride)):
         if v < 0:
             raise ValueError(f"layernorm.{name}: {v} is negative")
-    rpb = rows_per_batch if rows_per_batch > 0 else M
-    b, s = divmod(M - 1, rpb)                               # the last row's batch and row in it
-    reach = b * x_batch_stride + s * ldx
-    if b > 0:                                               # a short last batch: the batch before it may reach further
-        reach = max(reach, (b - 1) * x_batch_stride + (rpb - 1) * ldx)
-    if reach + D > _room(x):
-        raise ValueError(f"layernorm.x: {M} rows of {D} (ldx {ldx}, {rpb} rows per batch, batch stride {x_batch_stride}) reach element "
-                         f"{reach + D} of {_room(x)} from its start")
-    if (M - 1) * ldy + D > _room(y):
-        raise ValueError(f"layernorm.y: {M} rows of {D} with ldy {ldy} do not fit ({_room(y)} elements from its start)")
+    _fit(x, _rows_reach(M, D, ldx, rows_per_batch, x_batch_stride), "layernorm.x", M, D, ldx, rows_per_batch, x_batch_stride)
+    _fit(y, _rows_reach(M, D, ldy), "layernorm.y", M, D, ldy)
+    nb = _batches(M, rows_per_batch)
     for name, t in mods.items():
-        if t is not None and b * ld_mod + D > _room(t):
-            raise ValueError(f"layernorm.{name}: {b + 1} batches of {D} with ld_mod {ld_mod} do not fit ({_room(t)} elements from its start)")
+        if t is not None:
+            _fit(t, _rows_reach(nb, D, ld_mod), "layernorm." + name, nb, D, ld_mod)
     for name, t in vecs.items():
-        if t is not None and D > _room(t):
-            raise ValueError(f"layernorm.{name}: expected at least {D} elements, got {_room(t)} from its start")
+        if t is not None:
+            _fit(t, D, "layernorm." + name)
 
 
 def _stepcache_room(x: torch.Tensor, dense: dict, B: int, rows_per_batch: int, cols: int, x_batch_stride: int, what: str) -> None:
@@ -702,8 +715,8 @@ def _stepcache_room(x: torch.Tensor, dense: dict, B: int, rows_per_batch: int, c
     if B <= 0 or rows_per_batch <= 0 or cols <= 0 or x_batch_stride < rows_per_batch * cols:
         return
     n = rows_per_batch * cols
-    if (B - 1) * x_batch_stride + n > _room(x):
-        raise ValueError(f"{what}.x: {B} images of {n} elements, batch stride {x_batch_stride}, do not fit ({_room(x)} elements from its start)")
+    _fit(x, _rows_reach(B * rows_per_batch, cols, cols, rows_per_batch, x_batch_stride), what + ".x", B * rows_per_batch, cols, cols, rows_per_batch,
+         x_batch_stride)
     for name, t in dense.items():
         if t is not None and (not t.is_contiguous() or t.numel() < B * n):
             raise ValueError(f"{what}.{name}: expected a contiguous tensor of at least {B * n} elements")
@@ -959,16 +972,7 @@ def conv3x3(x_pad: torch.Tensor, w: torch.Tensor, y: torch.Tensor, *, B: int, Ho
     a.resid = resid.data_ptr() if resid is not None else None
     a.B, a.Ho, a.Wo, a.Hp, a.Wp, a.Cin, a.Cout = B, Ho, Wo, Hp, Wp, Cin, Cout
     a.ldy, a.stride, a.oy, a.ox, a.act = ldy if ldy is not None else Cout, stride, oy, ox, act
-    if _recorder is not None:
-        s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s_ev.record()
-        check(lib.drag_conv3x3_bf16(ctypes.byref(a), _stream()), "drag_conv3x3_bf16")
-        e_ev.record()
-        _recorder.events.append((s_ev, e_ev, 2.0 * B * Ho * Wo * Cout * 9 * Cin))
-        _recorder.shapes.append((B * Ho * Wo, Cout, 9 * Cin))
-        _recorder.is_conv.append(True)
-        return y
-    check(lib.drag_conv3x3_bf16(ctypes.byref(a), _stream()), "drag_conv3x3_bf16")
+    _recorded(lambda: check(lib.drag_conv3x3_bf16(ctypes.byref(a), _stream()), "drag_conv3x3_bf16"), (B * Ho * Wo, Cout, 9 * Cin), True)
     return y
 
 
@@ -1106,16 +1110,7 @@ def conv2d_f32(x: torch.Tensor, w: torch.Tensor, y: torch.Tensor, *, B: int, Hi:
     a.resid = resid.data_ptr() if resid is not None else None
     a.B, a.Hi, a.Wi, a.Cin, a.ldx, a.Ho, a.Wo, a.Cout, a.ldy, a.ld_add, a.ld_res = B, Hi, Wi, Cin, ldx, Ho, Wo, Cout, ldy, ld_add, ld_res
     a.KH, a.KW, a.stride, a.pad, a.pad_mode, a.transposed, a.act = KH, KW, stride, pad, pad_mode, int(transposed), act
-    if _recorder is not None and _recorder.f32:
-        s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s_ev.record()
-        check(lib.drag_conv2d_f32(ctypes.byref(a), _stream()), "drag_conv2d_f32")
-        e_ev.record()
-        _recorder.events.append((s_ev, e_ev, 2.0 * B * Ho * Wo * Cout * KH * KW * Cin))
-        _recorder.shapes.append((B * Ho * Wo, Cout, KH * KW * Cin))
-        _recorder.is_conv.append("f32")
-        return y
-    check(lib.drag_conv2d_f32(ctypes.byref(a), _stream()), "drag_conv2d_f32")
+    _recorded(lambda: check(lib.drag_conv2d_f32(ctypes.byref(a), _stream()), "drag_conv2d_f32"), (B * Ho * Wo, Cout, KH * KW * Cin), "f32")
     return y
 
 
@@ -1172,11 +1167,6 @@ def attention_small_f32(qkv, out, B: int, T: int, H: int, hd: int, ld: int, ldo:
     check(_lib.load().drag_attention_small_f32(_p(qkv), _p(out), B, T, H, hd, ld, ldo, scale, _stream()), "drag_attention_small_f32")
 
 
-def _room(t: torch.Tensor) -> int:
-    """elements of ``t``'s storage from its first element on"""
-    return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
-
-
 def textenc_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, B: int, S: int, H: int, *, ld: int,
                       batch_stride: int, scale: float, rel_bias: torch.Tensor | None = None, causal: bool = False, eager: bool,
                       ld_o: int | None = None, o_batch_stride: int | None = None) -> torch.Tensor:
@@ -1188,12 +1178,10 @@ def textenc_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: to
         _need(t, torch.bfloat16, f"textenc_attention.{n}")
     ld_o = H * 64 if ld_o is None else ld_o
     o_batch_stride = S * ld_o if o_batch_stride is None else o_batch_stride
-    span = (B - 1) * batch_stride + (S - 1) * ld + H * 64
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
-        if span > _room(t):
-            raise ValueError(f"textenc_attention.{n}: {B} x {S} rows of stride {ld} / {batch_stride} do not fit the buffer")
-    if (B - 1) * o_batch_stride + (S - 1) * ld_o + H * 64 > _room(out):
-        raise ValueError("textenc_attention.out: the output rows do not fit the destination")
+        _fit(t, _rows_reach(B * S, H * 64, ld, S, batch_stride), f"textenc_attention.{n}: the rows do not fit the buffer", B * S, H * 64, ld, S, batch_stride)
+    _fit(out, _rows_reach(B * S, H * 64, ld_o, S, o_batch_stride), "textenc_attention.out: the output rows do not fit the destination",
+         B * S, H * 64, ld_o, S, o_batch_stride)
     if rel_bias is not None:
         _need(rel_bias, torch.bfloat16, "textenc_attention.rel_bias")
         if tuple(rel_bias.shape) != (H, 2 * S - 1) or not rel_bias.is_contiguous():

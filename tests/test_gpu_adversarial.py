@@ -411,7 +411,7 @@ def test_gemm_split_k_stacked_launch_on_outliers(gpu, M, N, K):
     a, w = _bf(a).to(gpu), _bf(w).to(gpu)
     bias = _bf(torch.randn(N, generator=g)).to(gpu)
     ops.gemm(a[:256], w[:256])                                 # (registers the workspace)
-    args, _, _ = ops._gemm_args(a, w, None, bias, ops.ACT_NONE, 0, None, None, False, None, 0, 0, None, 0, 0, None, 0, None, 0, 0)
+    args, _, _ = ops._gemm_args(a, w, bias=bias)
     assert _lib.load().drag_gemm_bf16_splitk_slices(ctypes.byref(args)) >= 2
     out = ops.gemm(a, w, bias=bias)
     _gemm_check_gpu(out, a, w, bias=bias, what=f"split-K, outliers in one slice ({M}, {N}, {K})")
@@ -451,8 +451,8 @@ def test_gemm_pair_split_k_on_outliers(gpu):
     a1, a2, w1, w2 = _bf(a1).to(gpu), _bf(a2).to(gpu), _bf(w1).to(gpu), _bf(w2).to(gpu)
     o1 = torch.empty(M1, N, dtype=torch.bfloat16, device=gpu); o2 = torch.empty(M2, N, dtype=torch.bfloat16, device=gpu)
     ops.gemm(a1[:256], w1[:256])
-    g1, _, _ = ops._gemm_args(a1, w1, None, None, ops.ACT_NONE, 0, None, None, False, None, 0, 0, None, 0, 0, None, 0, None, 0, 0)
-    g2, _, _ = ops._gemm_args(a2, w2, None, None, ops.ACT_NONE, 0, None, None, False, None, 0, 0, None, 0, 0, None, 0, None, 0, 0)
+    g1, _, _ = ops._gemm_args(a1, w1)
+    g2, _, _ = ops._gemm_args(a2, w2)
     assert _lib.load().drag_gemm_bf16_pair_splitk_slices(ctypes.byref(g1), ctypes.byref(g2)) >= 2
     ops.gemm_pair(dict(a=a1, w=w1, out=o1), dict(a=a2, w=w2, out=o2))
     _gemm_check_gpu(o1, a1, w1, what="pair split-K, loud problem")
@@ -829,3 +829,56 @@ def test_vae_on_extreme_images_and_latents(gpu):
             e, e_or = _rel(got[b:b + 1], ref32), _rel(refbf, ref32)
             print(f"[adversarial] vae decode latents {b}: HIP-f32 {e:.3e} | bf16 oracle-f32 {e_or:.3e} | ratio {e / max(e_or, 1e-30):.2f}", flush=True)
             assert e < max(1e-2, 1.3 * e_or), (b, e, e_or)
+
+
+# ------------------------------------------------------------------ operand room of the bf16 GEMM (ops._rows_reach / ops._fit)
+def _gemm_exact_room_launch(gpu):
+    """a batched launch (M = 5 rows in batches of 4, N = 8, K = 64) in which every operand's storage ends with the last element that the
+    launch addresses: (keywords of ``ops.gemm``, {operand: elements}, the dense operands for the float64 yardstick)"""
+    from domain_rag_amd import ops
+    M, N, K, rpb = 5, 8, 64, 4
+    lda, a_bs, ldc, c_bs, ldg = 72, 4 * 72, 16, 4 * 16 + 8, 16
+    room = dict(a=ops._rows_reach(M, K, lda, rpb, a_bs), out=ops._rows_reach(M, N, ldc, rpb, c_bs), gate=ops._rows_reach(2, N, ldg), bias=N)
+    assert room == dict(a=288 + K, out=72 + N, gate=ldg + N, bias=N)                       # the last row is row 0 of batch 1
+    room["resid"] = room["out"]
+    g = _g(5)
+    a_rows, w, bias = _bf(torch.randn(M, K, generator=g)), _bf(torch.randn(N, K, generator=g)), _bf(torch.randn(N, generator=g))
+    a = torch.full((room["a"],), float("nan"), dtype=torch.bfloat16)
+    gate = torch.full((room["gate"],), float("nan"), dtype=torch.bfloat16)
+    for r in range(M):
+        a[(r // rpb) * a_bs + (r % rpb) * lda:][:K] = a_rows[r]
+    gate[:N], gate[ldg:ldg + N] = 1.0, 2.0              # powers of two over a zero residual: each row is its batch's multiple of the plain product
+    kw = dict(a=a.to(gpu), w=w.to(gpu), out=torch.full((room["out"],), -7.0, dtype=torch.bfloat16, device=gpu), bias=bias.to(gpu),
+              gate=gate.to(gpu), resid=torch.zeros(room["resid"], dtype=torch.bfloat16, device=gpu), M=M, a_rows_per_batch=rpb, a_batch_stride=a_bs,
+              lda=lda, c_rows_per_batch=rpb, c_batch_stride=c_bs, ldc=ldc, ldg=ldg)
+    for name, n in room.items():
+        assert ops._room(kw[name]) == n, name
+    return kw, room, (a_rows.to(gpu), bias.to(gpu))
+
+
+def test_gemm_passes_where_every_operand_has_exactly_the_room_it_reaches(gpu):
+    from domain_rag_amd import ops
+    kw, room, (a_rows, bias) = _gemm_exact_room_launch(gpu)
+    out = ops.gemm(**kw)
+    M, N, rpb, ldc, c_bs = kw["M"], 8, 4, kw["ldc"], kw["c_batch_stride"]
+    offs = [(r // rpb) * c_bs + (r % rpb) * ldc for r in range(M)]
+    got = torch.stack([out[o:o + N] / (1.0 + r // rpb) for r, o in enumerate(offs)])       # (the gate: 1 in batch 0, 2 in batch 1)
+    _gemm_check_gpu(got, a_rows, kw["w"], bias=bias, what="room == reach")
+    owned = torch.zeros(room["out"], dtype=torch.bool, device=gpu)
+    for o in offs:
+        owned[o:o + N] = True
+    assert (out[~owned] == -7.0).all()
+
+
+@pytest.mark.parametrize("short", ["a", "out", "resid", "gate", "bias"])
+def test_gemm_refuses_an_operand_one_element_short_of_its_reach(gpu, short):
+    """refused before anything is launched: the batched destination and the operands that only the MXFP8 route used to check"""
+    from domain_rag_amd import ops
+    kw, room, _ = _gemm_exact_room_launch(gpu)
+    kw[short] = torch.zeros(room[short] - 1, dtype=torch.bfloat16, device=gpu)
+    before = kw["out"].clone()
+    with pytest.raises(ValueError, match=rf"gemm\.{short}"):
+        ops.gemm(**kw)
+    with pytest.raises(ValueError, match=rf"gemm\.{short}"):
+        ops.gemm_pair(kw, kw)
+    assert torch.equal(kw["out"], before)

@@ -1123,8 +1123,7 @@ def test_gemm_split_k_equals_one_launch_to_the_last_bf16_bit_or_so(gpu, M, N, K,
         return [o.cpu() for o in outs]
 
     def slices(**kw):
-        args, _, _ = ops._gemm_args(a, w, None, kw.get("bias"), kw.get("act", ops.ACT_NONE), 0, None, None, kw.get("out_f32", False), kw.get("M"), 0, 0, None, 0, 0, None, 0,
-                                    None, 0, 0)
+        args, _, _ = ops._gemm_args(a, w, **kw)
         return _lib.load().drag_gemm_bf16_splitk_slices(ctypes.byref(args))
     ops.gemm(a[:256], w[:256])                       # (registers the workspace)
     with ops.options(gemm_splitk=0):
@@ -1173,8 +1172,8 @@ def test_gemm_pair_split_k_is_one_partial_launch_over_both_problems(gpu, M1, M2,
         ref = run()
     with ops.options(gemm_splitk=0):
         got = run()
-        a1, _, _ = ops._gemm_args(p1["a"], p1["w"], None, None, ops.ACT_NONE, 0, None, None, False, None, 0, 0, None, 0, 0, None, 0, None, 0, 0)
-        a2, _, _ = ops._gemm_args(p2["a"], p2["w"], None, None, ops.ACT_NONE, 0, None, None, False, None, 0, 0, None, 0, 0, None, 0, None, 0, 0)
+        a1, _, _ = ops._gemm_args(p1["a"], p1["w"])
+        a2, _, _ = ops._gemm_args(p2["a"], p2["w"])
         assert _lib.load().drag_gemm_bf16_pair_splitk_slices(ctypes.byref(a1), ctypes.byref(a2)) >= 2
     for (x, y, pr) in ((ref[0], got[0], p1), (ref[1], got[1], p2)):
         v64 = pr["a"].double() @ pr["w"].double().T + pr["bias"].double()
@@ -1184,3 +1183,16 @@ def test_gemm_pair_split_k_is_one_partial_launch_over_both_problems(gpu, M1, M2,
         assert torch.isfinite(y.float()).all() and (d <= tol).all(), float((d / tol).max())
         assert (x.double() - exact).abs().max() * 1.05 + 1e-2 >= (y.double() - exact).abs().max()
 
+
+def test_gemm_pair_takes_gemm_keywords_but_no_second_destination(gpu):
+    from domain_rag_amd import ops
+    a, w = _randn((8, 64), 1).to(gpu), _randn((8, 64), 2).to(gpu)
+    with pytest.raises(TypeError, match="no_such_keyword"):
+        ops.gemm_pair(dict(a=a, w=w, no_such_keyword=1), dict(a=a, w=w))
+    with pytest.raises(TypeError, match="no_such_keyword"):
+        ops.gemm_pair(dict(a=a, w=w), dict(a=a, w=w, no_such_keyword=1))
+    for two_dest in (dict(out2=torch.empty_like(a)), dict(ldc2=8), dict(n_split=256)):
+        with pytest.raises(TypeError, match=next(iter(two_dest))):
+            ops.gemm_pair(dict(a=a, w=w), dict(a=a, w=w, **two_dest))
+    o1, o2 = ops.gemm_pair(dict(a=a, w=w), dict(a=a, w=w, bias=None))
+    assert torch.equal(o1, ops.gemm(a, w)) and torch.equal(o2, o1)

@@ -204,3 +204,18 @@ def test_argument_checks(gpu):
         ops.gemm_mxfp8(u8(16, 128), u8(16, 4), u8(16, 128), u8(16, 4), out, resid=torch.zeros(8, 16, dtype=torch.bfloat16, device=gpu))
     with pytest.raises(ValueError, match="2-D"):
         ops.quantize_mxfp8(torch.zeros(2, 4, 128, dtype=torch.bfloat16, device=gpu))
+
+
+def test_a_short_last_batch_is_checked_against_the_full_batch_before_it(gpu):
+    """K = 128, five rows in batches of four that lie 8 elements apart: the last row ends at element 136, row 3 of batch 0 at 512"""
+    from domain_rag_amd import ops
+    short = torch.zeros(136 + 8, dtype=torch.bfloat16, device=gpu)
+    with pytest.raises(ValueError, match=r"quantize_mxfp8\.x"):
+        ops.quantize_mxfp8(short, M=5, K=128, lda=128, rows_per_batch=4, batch_stride=8)
+    u8 = lambda *s: torch.zeros(*s, dtype=torch.uint8, device=gpu)
+    operands = (u8(5, 128), u8(5, 4), u8(128, 128), u8(128, 4))
+    with pytest.raises(ValueError, match=r"gemm_mxfp8\.out"):
+        ops.gemm_mxfp8(*operands, short, M=5, ldc=128, c_rows_per_batch=4, c_batch_stride=8)
+    with pytest.raises(ValueError, match=r"gemm_mxfp8\.resid"):
+        ops.gemm_mxfp8(*operands, torch.zeros(512, dtype=torch.bfloat16, device=gpu), resid=short, M=5, ldc=128, c_rows_per_batch=4, c_batch_stride=8)
+    assert not short.any()
