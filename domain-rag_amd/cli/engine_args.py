@@ -1,6 +1,8 @@
 """The flags stages 2 and 3 share, declared once, and the :class:`..engine.Engine` they describe (``--model_root`` stays with a stage's directory flags)."""
 from __future__ import annotations
 
+import os
+
 from ..engine import Engine
 from ..step_cache import parse_step_cache, parse_step_cache_count, parse_step_cache_order
 
@@ -33,6 +35,9 @@ def add_engine_arguments(p, batch_flag: str, steps: int, tiny: str, png_files: s
                         "image); 0 = no limit; default: $DRAG_STEP_CACHE_MAX_RUN, else 0")
     p.add_argument("--step_cache_warmup", type=lambda v: parse_step_cache_count(v, "warmup"), default=None, metavar="N",
                    help="when --step_cache is on: the first N steps of a denoise loop compute; default: $DRAG_STEP_CACHE_WARMUP, else 0")
+    p.add_argument("--lora", action="append", default=None, metavar="PATH[:SCALE]",
+                   help="merge a LoRA adapter (.safetensors, diffusers / PEFT or kohya spelling) into the DiT's weights at SCALE (default 1.0); "
+                        "repeatable, merged in the order given; default: none")
     p.add_argument("--text_encoder", choices=["transformers", "hip"], default="transformers",
                    help="what encodes a prompt without a prompt_cache file: the transformers T5 / CLIP modules (eager torch) or the HIP "
                         "encoders (domain_rag_amd.textenc); tokenizers are host Python either way")
@@ -56,7 +61,14 @@ def pipe_attention_precision(pipe) -> str:
     return getattr(getattr(pipe, "tr", None), "attention_precision", "bf16")
 
 
+def pipe_loras(pipe) -> list:
+    """[{"file": base name, "scale": s}, ...] of the LoRA adapters merged into a pipeline's DiT (empty without one), for the stages' two
+    parameter writers"""
+    tr = getattr(pipe, "tr", None)
+    return [{"file": os.path.basename(e["adapter"].path or n), "scale": e["scale"]} for n, e in getattr(tr, "_loras", {}).items()]
+
+
 def engine_from_args(kind: str, args, device) -> Engine:
     return Engine(kind, args.model_root, synthetic=args.synthetic_weights, tiny=args.tiny, device=device, text_encoder=args.text_encoder,
                   linear_precision=args.linear_precision, attention_precision=args.attention_precision, step_cache=args.step_cache, step_cache_scope=args.step_cache_scope,
-                  step_cache_order=args.step_cache_order, step_cache_max_run=args.step_cache_max_run, step_cache_warmup=args.step_cache_warmup)
+                  step_cache_order=args.step_cache_order, step_cache_max_run=args.step_cache_max_run, step_cache_warmup=args.step_cache_warmup, lora=getattr(args, "lora", None))

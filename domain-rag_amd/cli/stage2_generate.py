@@ -21,7 +21,7 @@ import torch
 from ..engine import Engine, generator_noise, pack_noise
 from .. import hostlogic as H
 from ..retrieval import shard_bounds
-from .engine_args import add_engine_arguments, engine_from_args, pipe_attention_precision, pipe_step_cache_switches
+from .engine_args import add_engine_arguments, engine_from_args, pipe_attention_precision, pipe_loras, pipe_step_cache_switches
 
 COCO_IMAGE_SCALE, TARGET_IMAGE_SCALE, COCO_TEXT_SCALE, TARGET_TEXT_SCALE = 0.8, 1.0, 1.0, 1.0
 PROMPT = ""
@@ -63,6 +63,11 @@ def params_txt_step_cache(step_cache, scope: str = "batch", order: int = 0, max_
 def params_txt_attention_precision(precision: str) -> str:
     """the line params.txt gains when the DiT's attention runs in MXFP8; nothing in bf16 (the file is then byte-identical to the reference's)"""
     return f"注意力精度: {precision}\n" if precision == "mxfp8" else ""
+
+
+def params_txt_lora(loras: list) -> str:
+    """the line params.txt gains when LoRA adapters are merged into the DiT; nothing without one (the file is then byte-identical to the reference's)"""
+    return "LoRA: " + ", ".join(f"{a['file']}:{a['scale']}" for a in loras) + "\n" if loras else ""
 
 
 def generate_ranked(engine: Engine, target_path, items, sdir, args, database):
@@ -123,7 +128,8 @@ def generate_ranked(engine: Engine, target_path, items, sdir, args, database):
                                 f"参考文本权重: {COCO_TEXT_SCALE}\n目标文本权重: {TARGET_TEXT_SCALE}\n提示词: {PROMPT}\n指导比例: {GUIDANCE}\n"
                                 f"推理步数: {args.num_inference_steps}\n生成图像尺寸: {w}x{h}\n原始图像尺寸: {tgt_img.size[0]}x{tgt_img.size[1]}\n"
                                 + params_txt_step_cache(*pipe_step_cache_switches(engine.pipe))
-                                + params_txt_attention_precision(pipe_attention_precision(engine.pipe)))
+                                + params_txt_attention_precision(pipe_attention_precision(engine.pipe))
+                                + params_txt_lora(pipe_loras(engine.pipe)))
                 rs = f"rank{rank}" if rank is not None else ""
                 ss = f"_sim{similarity:.4f}" if similarity is not None else ""
                 with open(os.path.join(sdir, f"ref_info{rs}{ss}.txt"), "w") as f:

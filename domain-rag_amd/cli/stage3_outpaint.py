@@ -28,7 +28,7 @@ import torch
 from .. import hostlogic as H
 from ..engine import Engine, generator_noise, pack_noise
 from ..io_pool import ImageWriter
-from .engine_args import add_engine_arguments, engine_from_args, pipe_attention_precision, pipe_step_cache_switches
+from .engine_args import add_engine_arguments, engine_from_args, pipe_attention_precision, pipe_loras, pipe_step_cache_switches
 
 RESULT_DIR, DATASETS_DIR = "./result", "./datasets"
 
@@ -264,6 +264,8 @@ def process_sample(engine: Engine, args, dataset, sample_id, sample_dir, shot, p
                 params.update(step_cache_params(*pipe_step_cache_switches(engine.pipe)))
                 if pipe_attention_precision(engine.pipe) == "mxfp8":      # (absent in bf16: the file is then the reference's)
                     params["attention_precision"] = "mxfp8"
+                if pipe_loras(engine.pipe):                               # (absent without an adapter, for the same reason)
+                    params["lora"] = pipe_loras(engine.pipe)
                 params_path = os.path.join(out_dir, f"{prefix}_params{suffix}.json")
                 with open(params_path, "w") as f:
                     json.dump(params, f, indent=2)

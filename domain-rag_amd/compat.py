@@ -156,6 +156,64 @@ class _FluxPipe(_Pipe):
             vp = load_safetensors_dir(os.path.join(self._path, "vae"))
         self.cfg = cfg
         self.tr, self.vae = FluxTransformerHIP(cfg, tp, dev), vae_mod.FluxVaeHIP(vcfg, vp, dev)
+        queued, self._lora_queue = getattr(self, "_lora_queue", []), []
+        for call, args in queued:                           # adapter calls made before .to("cuda")
+            getattr(self, call)(*args)
+
+    # diffusers' FluxLoraLoaderMixin, as far as a merged adapter has a meaning for it: adapters are always merged into the DiT's resident
+    # weights (FluxTransformerHIP.load_lora), so fuse_lora / unfuse_lora change nothing and the per-adapter weights of set_adapters are
+    # merge scales.  A call before .to("cuda") is queued and applied when the model is built.
+    def _lora_call(self, call, *args) -> bool:
+        if self._built or getattr(self, "tr", None) is not None:
+            return False
+        self.__dict__.setdefault("_lora_queue", []).append((call, args))
+        return True
+
+    def load_lora_weights(self, pretrained_model_name_or_path_or_dict, weight_name=None, adapter_name=None, **_):
+        path = pretrained_model_name_or_path_or_dict
+        if isinstance(path, dict):
+            raise NotImplementedError("load_lora_weights takes a file or a directory here, not a state dict")
+        path = os.fspath(path)
+        if os.path.isdir(path):
+            if weight_name is None:
+                files = sorted(f for f in os.listdir(path) if f.endswith(".safetensors"))
+                if len(files) != 1:
+                    raise ValueError(f"{path} holds {len(files)} .safetensors files: pass weight_name")
+                weight_name = files[0]
+            path = os.path.join(path, weight_name)
+        if self._lora_call("load_lora_weights", path, None, adapter_name):
+            return
+        if adapter_name is None:                            # diffusers' default names: default_0, default_1, ...
+            adapter_name = f"default_{len(self.tr.loras)}"
+        self.tr.load_lora(path, 1.0, adapter_name)
+
+    def set_adapters(self, adapter_names, adapter_weights=None):
+        """the named adapters at ``adapter_weights`` (one number, or one per name; None: 1.0); a loaded adapter that is not named is
+        switched off (merged at scale 0)"""
+        if self._lora_call("set_adapters", adapter_names, adapter_weights):
+            return
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        weights = adapter_weights if isinstance(adapter_weights, (list, tuple)) else [1.0 if adapter_weights is None else adapter_weights] * len(names)
+        if len(weights) != len(names):
+            raise ValueError(f"{len(names)} adapter names but {len(weights)} weights")
+        loaded = [a["name"] for a in self.tr.loras]
+        missing = [n for n in names if n not in loaded]
+        if missing:
+            raise ValueError(f"adapters {missing} are not loaded (loaded: {loaded})")
+        for n in loaded:
+            self.tr.set_lora_scale(n, float(weights[names.index(n)]) if n in names else 0.0)
+
+    def unload_lora_weights(self):
+        if self._lora_call("unload_lora_weights"):
+            return
+        self.tr.unload_lora()
+
+    def fuse_lora(self, lora_scale=1.0, **_):
+        if float(lora_scale) != 1.0:
+            raise ValueError("fuse_lora(lora_scale != 1.0): adapters are always merged here; set their scales with set_adapters(names, adapter_weights)")
+
+    def unfuse_lora(self, **_):
+        pass
 
     @staticmethod
     def _to_pil(out_u8):

@@ -22,6 +22,7 @@ from .denoise import DenoisePipeline
 from .fill_pipeline import FluxFillHIP
 from .flux import FluxTransformerHIP, latent_image_ids
 from .flux_params import FluxConfig, init_params, load_safetensors_dir
+from .lora import lora_spec
 from .scheduler import flow_sigmas
 
 TINY = dict(flux=dict(num_layers=1, num_single_layers=1, num_attention_heads=2, joint_attention_dim=256, pooled_projection_dim=64),
@@ -189,7 +190,7 @@ class Engine:
                  seed: int = 0, text_encoder: str = "transformers", linear_precision: str | None = None, attention_precision: str | None = None,
                  step_cache: float | None = None,
                  step_cache_scope: str | None = None, step_cache_order: int | None = None, step_cache_max_run: int | None = None,
-                 step_cache_warmup: int | None = None):
+                 step_cache_warmup: int | None = None, lora=None):
         """``text_encoder``: what encodes a prompt-cache miss — "transformers" (the reference's modules, eager torch) or "hip"
         (:mod:`.textenc`; with ``synthetic``: seeded encoders and stand-in tokenizers, results kept in memory).
         ``linear_precision``: the DiT blocks' Linears, "bf16" or "mxfp8" (None: $DRAG_LINEAR_PRECISION, else bf16; :mod:`.flux`).
@@ -199,7 +200,9 @@ class Engine:
         "image" (every image for itself; None: $DRAG_STEP_CACHE_SCOPE, else "batch") — the pipeline's ``step_cache_scope``;
         ``step_cache_order``: what a reused step adds, 0 (the cached residual) or 1 (its first-order forecast); ``step_cache_max_run`` /
         ``step_cache_warmup``: after that many reused steps in a row the next one computes / the first that many steps compute (0: no
-        limit; None: $DRAG_STEP_CACHE_ORDER / _MAX_RUN / _WARMUP, else 0) — the pipeline's attributes of the same names"""
+        limit; None: $DRAG_STEP_CACHE_ORDER / _MAX_RUN / _WARMUP, else 0) — the pipeline's attributes of the same names.
+        ``lora``: LoRA adapters merged into the DiT once it is built, in order: ``"PATH[:SCALE]"`` strings or (path, scale) pairs
+        (:meth:`.flux.FluxTransformerHIP.load_lora`; None or empty: none, and nothing about the model changes)"""
         assert kind in ("dev", "fill")
         if text_encoder not in ("transformers", "hip"):
             raise ValueError(f"text_encoder must be 'transformers' or 'hip', not {text_encoder!r}")
@@ -241,6 +244,18 @@ class Engine:
             load = load_text_encoders_hip if text_encoder == "hip" else load_text_encoders
             self.text = TextCache(model_root, synthetic, Lt, J, P, dev,
                                   loader=(lambda: load(flux_dir, dev)) if os.path.isdir(os.path.join(flux_dir, "text_encoder_2")) else None)
+        for item in lora or ():
+            self.load_lora(*lora_spec(item))
+
+    # LoRA adapters of the DiT (merged into its resident weights: flux.FluxTransformerHIP.load_lora)
+    def load_lora(self, adapter_or_path, scale: float = 1.0, name: str | None = None) -> str:
+        return self.pipe.tr.load_lora(adapter_or_path, scale, name)
+
+    def unload_lora(self, name: str | None = None) -> None:
+        self.pipe.tr.unload_lora(name)
+
+    def set_lora_scale(self, name: str, scale: float) -> None:
+        self.pipe.tr.set_lora_scale(name, scale)
 
     def prior_embeds(self, pil_images, prompt: str, embeds_scale, pooled_scale):
         """pipe_prior_redux(images, prompt=…, prompt_2="", prompt_embeds_scale=…, pooled_prompt_embeds_scale=…)"""

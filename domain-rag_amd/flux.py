@@ -75,6 +75,45 @@ def latent_image_ids(h: int, w: int) -> torch.Tensor:
     return ids.reshape(h * w, 3)
 
 
+def linear_locations(cfg: FluxConfig) -> dict:
+    """Where :class:`FluxTransformerHIP` keeps each Linear weight: every 2-D name of ``flux_params.param_shapes(cfg)`` ->
+    ``(holder, row0, rows)``.  A holder names one resident tensor: ``("w", name)`` = ``model.w[name]``, ``("double", i, key)`` /
+    ``("single", i, key)`` = ``model.double[i][key]`` / ``model.single[i][key]`` (the stacked ``wqkv`` / ``cwqkv`` / ``wqkvm`` hold
+    several names as row ranges), ``("mod_w",)`` = the stacked modulation matrix, whose row offsets are ``model.mod_off``'s.  A pure
+    function of the config (the constructor's layout, restated); LoRA adapters find their targets with it."""
+    D, F = cfg.dim, cfg.mlp_ratio * cfg.dim
+    loc: dict = {}
+    names = ["x_embedder", "context_embedder", "proj_out", "time_text_embed.timestep_embedder.linear_1",
+             "time_text_embed.timestep_embedder.linear_2", "time_text_embed.text_embedder.linear_1", "time_text_embed.text_embedder.linear_2"]
+    if cfg.guidance_embeds:
+        names += ["time_text_embed.guidance_embedder.linear_1", "time_text_embed.guidance_embedder.linear_2"]
+    rows_of = {"x_embedder": D, "context_embedder": D, "proj_out": cfg.out_channels}
+    for n in names:
+        loc[n + ".weight"] = (("w", n + ".weight"), 0, rows_of.get(n, D))
+    off = 0
+    for i in range(cfg.num_layers):
+        p = f"transformer_blocks.{i}."
+        for nm in ("norm1", "norm1_context"):
+            loc[p + nm + ".linear.weight"] = (("mod_w",), off, 6 * D)
+            off += 6 * D
+        for key, parts in (("wqkv", ("attn.to_q", "attn.to_k", "attn.to_v")), ("cwqkv", ("attn.add_q_proj", "attn.add_k_proj", "attn.add_v_proj"))):
+            for j, n in enumerate(parts):
+                loc[p + n + ".weight"] = (("double", i, key), j * D, D)
+        for key, n, rows in (("wo", "attn.to_out.0", D), ("cwo", "attn.to_add_out", D), ("w1", "ff.net.0.proj", F), ("w2", "ff.net.2", D),
+                             ("cw1", "ff_context.net.0.proj", F), ("cw2", "ff_context.net.2", D)):
+            loc[p + n + ".weight"] = (("double", i, key), 0, rows)
+    for i in range(cfg.num_single_layers):
+        p = f"single_transformer_blocks.{i}."
+        loc[p + "norm.linear.weight"] = (("mod_w",), off, 3 * D)
+        off += 3 * D
+        for j, n in enumerate(("attn.to_q", "attn.to_k", "attn.to_v")):
+            loc[p + n + ".weight"] = (("single", i, "wqkvm"), j * D, D)
+        loc[p + "proj_mlp.weight"] = (("single", i, "wqkvm"), 3 * D, F)
+        loc[p + "proj_out.weight"] = (("single", i, "wo"), 0, D)
+    loc["norm_out.linear.weight"] = (("mod_w",), off, 2 * D)
+    return loc
+
+
 class FluxTransformerHIP:
     def __init__(self, cfg: FluxConfig, params: dict, device="cuda", linear_precision: str | None = None,
                  attention_precision: str | None = None):
@@ -153,6 +192,8 @@ class FluxTransformerHIP:
         self._ws_key = None
         self._rope_key = None
         self._mx_ready = False
+        self._loras: dict = {}           # name -> {"adapter", "scale"}: the active LoRA adapters, in load order
+        self._pristine: dict = {}        # holder -> a copy of the resident tensor as built, while an adapter touches it
         self.linear_precision = linear_precision or _LINEAR_PRECISION
         self.attention_precision = attention_precision or _ATTENTION_PRECISION
 
@@ -244,6 +285,111 @@ class FluxTransformerHIP:
             return
         self._mx_gemm(ws, d1, blk[key1 + "@mx"])
         self._mx_gemm(ws, d2, blk[key2 + "@mx"], row0=d1["M"])
+
+    # ------------------------------------------------------------------ LoRA adapters
+    # Adapters are MERGED into the resident bf16 weights, in place (ops.lora_merge; the rule: lora.py): a forward with an adapter launches
+    # what it launches without one, and a captured graph, which holds the weights' addresses, replays the new values.  Every change
+    # re-merges each touched Linear from a pristine copy of its tensor, one launch over the concatenated ranks of all active adapters on
+    # it, so the resident bits depend on the active set only, never on what was loaded before, and an unload is exact.  Adapters do not
+    # change inside a denoise loop: the pipelines reset their step cache per call, so a cache never spans two adapter states.
+    def _holder(self, holder):
+        if holder[0] == "w":
+            return self.w[holder[1]]
+        if holder[0] == "mod_w":
+            return self.mod_w
+        return (self.double if holder[0] == "double" else self.single)[holder[1]][holder[2]]
+
+    @property
+    def loras(self) -> list:
+        """the active adapters, in load order: name, scale, the ranks the file holds, the number of Linears it targets"""
+        return [dict(name=n, scale=e["scale"], ranks=e["adapter"].ranks, targets=len(e["adapter"].entries)) for n, e in self._loras.items()]
+
+    def load_lora(self, adapter_or_path, scale: float = 1.0, name: str | None = None) -> str:
+        """Merge a LoRA adapter (a :class:`.lora.Adapter`, or the path of a ``.safetensors`` file in the diffusers / PEFT or the kohya
+        spelling) into the resident weights at ``scale``; returns its name (``name``; None: the file's base name, else ``lora``, with ``_1``,
+        ``_2``, ... appended while that name is taken).  Loading under a ``name`` that is loaded already replaces that adapter.  Not while a
+        stream is capturing."""
+        from . import lora
+        ad = adapter_or_path if isinstance(adapter_or_path, lora.Adapter) else lora.read_adapter(os.fspath(adapter_or_path), self.cfg)
+        loc = linear_locations(self.cfg)
+        bad = [n for n, (down, up, _) in ad.entries.items() if n not in loc or (up.shape[0], down.shape[1]) != (loc[n][2], self._holder(loc[n][0]).shape[1])]
+        if bad:
+            raise ValueError(f"LoRA adapter: entries that fit no Linear of this DiT: {', '.join(sorted(bad)[:8])}")
+        if name is None:
+            base = os.path.splitext(os.path.basename(ad.path))[0] if ad.path else "lora"
+            name, k = base, 0
+            while name in self._loras:
+                k += 1
+                name = f"{base}_{k}"
+        touched = set(ad.entries) | (set(self._loras[name]["adapter"].entries) if name in self._loras else set())
+        self._lora_guard()
+        self._loras.pop(name, None)
+        self._loras[name] = dict(adapter=ad, scale=float(scale))
+        self._lora_remerge(touched)
+        return name
+
+    def unload_lora(self, name: str | None = None) -> None:
+        """take adapter ``name`` (None: every adapter) out of the weights: what it touched is merged again from the pristine copy with the
+        adapters that remain, or copied back from it when none does — bit for bit the weights of a model that never saw it"""
+        names = list(self._loras) if name is None else [name]
+        if name is not None and name not in self._loras:
+            raise KeyError(f"no LoRA adapter named {name!r} (loaded: {list(self._loras)})")
+        self._lora_guard()
+        touched = set()
+        for n in names:
+            touched |= set(self._loras.pop(n)["adapter"].entries)
+        self._lora_remerge(touched)
+
+    def set_lora_scale(self, name: str, scale: float) -> None:
+        """change the scale of a loaded adapter: the same bits as loading it at ``scale`` in the first place"""
+        if name not in self._loras:
+            raise KeyError(f"no LoRA adapter named {name!r} (loaded: {list(self._loras)})")
+        self._lora_guard()
+        self._loras[name]["scale"] = float(scale)
+        self._lora_remerge(set(self._loras[name]["adapter"].entries))
+
+    @staticmethod
+    def _lora_guard():
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("LoRA adapters cannot change while a stream is capturing (a graph replays weights, it does not merge them)")
+
+    def _lora_remerge(self, linears) -> None:
+        """bring the resident rows of every Linear in ``linears`` to the active set of adapters"""
+        loc = linear_locations(self.cfg)
+        dev = self.device
+        active_holders = {loc[n][0] for e in self._loras.values() for n in e["adapter"].entries}
+        changed = set()
+        for n in sorted(linears):
+            holder, row0, rows = loc[n]
+            w = self._holder(holder)
+            parts = [(e["adapter"].entries[n], e["scale"]) for e in self._loras.values() if n in e["adapter"].entries]
+            if holder not in self._pristine:
+                if not parts:
+                    continue                                # (never touched, or restored already)
+                self._pristine[holder] = w.clone()          # first touch: the tensor is still as built
+            w0 = self._pristine[holder]
+            changed.add(holder)
+            if not parts:
+                w[row0: row0 + rows].copy_(w0[row0: row0 + rows])
+                continue
+            R = sum(d.shape[0] for (d, _, _), _ in parts)
+            up = torch.zeros((rows, (R + 7) // 8 * 8), dtype=torch.bfloat16, device=dev)[:, :R]
+            down = torch.empty((R, w.shape[1]), dtype=torch.bfloat16, device=dev)
+            scale = torch.empty(R, dtype=torch.float32)
+            r0 = 0
+            for (d, u, factor), s in parts:
+                r = d.shape[0]
+                up[:, r0: r0 + r].copy_(u); down[r0: r0 + r].copy_(d)
+                scale[r0: r0 + r] = s * factor
+                r0 += r
+            ops.lora_merge(w0[row0: row0 + rows], w[row0: row0 + rows], up, down, scale.to(dev))
+        for holder in changed:
+            if holder[0] in ("double", "single"):
+                blk = (self.double if holder[0] == "double" else self.single)[holder[1]]
+                if holder[2] + "@mx" in blk:                # the MX copy follows, into the buffers it has
+                    ops.quantize_mxfp8(blk[holder[2]], out=blk[holder[2] + "@mx"])
+            if holder not in active_holders:
+                del self._pristine[holder]                  # (rows of it that an adapter touched were copied back above)
 
     # ------------------------------------------------------------------ workspaces
     def _workspace(self, B, St, Si):

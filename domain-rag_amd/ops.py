@@ -416,6 +416,41 @@ def quantize_mxfp8(x: torch.Tensor, *, M: int | None = None, K: int | None = Non
     return q, s
 
 
+def lora_merge(w0: torch.Tensor, w: torch.Tensor, up: torch.Tensor, down: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """``w <- bf16(f32(w0) + sum_r scale[r] * up[:, r] * down[r, :])`` (``drag_lora_merge_bf16``; the rule: :func:`.lora.merge_ref`):
+    ``w0`` / ``w`` bf16 [N, K], ``up`` bf16 [N, R], ``down`` bf16 [R, K], ``scale`` float32 [R], one factor per rank column.  Every matrix
+    may be a row-strided view with unit inner stride (a row slice of a stacked weight); ``w is w0`` (same address and row stride) merges in
+    place, otherwise the two must not overlap.  Not during stream capture: the launch changes weights that captured graphs only read."""
+    for t, name in ((w0, "w0"), (w, "w"), (up, "up"), (down, "down")):
+        _need(t, torch.bfloat16, "lora_merge." + name)
+        if t.dim() != 2 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+            raise ValueError(f"lora_merge.{name}: a 2-D matrix with unit inner stride and non-overlapping rows expected")
+    _need(scale, torch.float32, "lora_merge.scale")
+    N, K = w.shape
+    R = down.shape[0]
+    if tuple(w0.shape) != (N, K) or tuple(up.shape) != (N, R) or down.shape[1] != K or R < 1:
+        raise ValueError(f"lora_merge: w0 {tuple(w0.shape)}, w {tuple(w.shape)}, up {tuple(up.shape)}, down {tuple(down.shape)} do not fit "
+                         "[N, K], [N, K], [N, R], [R, K]")
+    if scale.dim() != 1 or scale.numel() != R or not scale.is_contiguous():
+        raise ValueError(f"lora_merge.scale: a dense vector of R = {R} factors expected, got {tuple(scale.shape)}")
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("lora_merge: not during stream capture (a merge belongs between forwards, not into a graph)")
+    # (a single row has no stride of its own: the width, rounded up to the 16-byte pieces the kernel moves)
+    ldw0, ldw, ldup, lddown = (t.stride(0) if t.shape[0] > 1 else -(-t.shape[1] // 8) * 8 for t in (w0, w, up, down))
+    _fit(w0, _rows_reach(N, K, ldw0), "lora_merge.w0", N, K, ldw0)
+    _fit(w, _rows_reach(N, K, ldw), "lora_merge.w", N, K, ldw)
+    _fit(up, _rows_reach(N, R, ldup), "lora_merge.up", N, R, ldup)
+    _fit(down, _rows_reach(R, K, lddown), "lora_merge.down", R, K, lddown)
+    if not (w.data_ptr() == w0.data_ptr() and ldw == ldw0):
+        a0, a1 = w0.data_ptr(), w0.data_ptr() + 2 * _rows_reach(N, K, ldw0)
+        b0, b1 = w.data_ptr(), w.data_ptr() + 2 * _rows_reach(N, K, ldw)
+        if a0 < b1 and b0 < a1:
+            raise ValueError("lora_merge: w and w0 overlap (only the in-place form, same address and row stride, may share memory)")
+    check(_lib.load().drag_lora_merge_bf16(_p(w0), ldw0, _p(w), ldw, N, K, _p(up), ldup, _p(down), lddown, _p(scale), R, _stream()),
+          "drag_lora_merge_bf16")
+    return w
+
+
 def gemm_mxfp8(aq: torch.Tensor, ascale: torch.Tensor, wq: torch.Tensor, wscale: torch.Tensor, out: torch.Tensor | None = None, *,
                bias=None, act: int = ACT_NONE, act_n0: int = 0, gate=None, resid=None, M: int | None = None,
                c_rows_per_batch: int = 0, c_batch_stride: int = 0, ldc: int | None = None, ldg: int = 0) -> torch.Tensor:

@@ -193,6 +193,23 @@ typedef struct drag_gemm_mx_args {
 int drag_gemm_mxfp8(const drag_gemm_mx_args* args, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * drag_lora_merge_bf16 — fold low-rank adapters into a resident bf16 weight (diffusers FluxPipeline.load_lora_weights / fuse_lora; the
+ * default path loads no adapter and never calls this):
+ *   w[n,k] = bf16( f32(w0[n,k]) + sum_{r<R} scale[r] * up[n,r] * down[r,k] )
+ * with the sum accumulated in float32 on the bf16 matrix cores (any order) and ONE rounding to bf16 (nearest-even) per element.  scale[r]
+ * * up[n,r] is formed in float32 and enters the matrix core as two bf16 terms (16 mantissa bits); down enters exactly.
+ * domain-rag_amd/lora.py merge_ref states the rule in float64.
+ *   w0, w: N rows of K bf16 elements, row strides ldw0 / ldw (elements); columns >= K of a row are neither read nor written.
+ *          w == w0 with ldw == ldw0 is the in-place form; otherwise the two must not overlap.
+ *   up:    [N, R] bf16, row stride ldup (the file's lora_B / lora_up); columns >= R of a padded row never contribute, whatever they hold.
+ *   down:  [R, K] bf16, row stride lddown (the file's lora_A / lora_down).
+ *   scale: R float32 on the device, one per rank column (several adapters on one Linear: one launch over their concatenated ranks).
+ * Requires non-null pointers, N >= 1, R >= 1, K >= 8 and K % 8 == 0, ldw / ldw0 / lddown >= K and % 8 == 0, ldup >= R and % 8 == 0,
+ * w0 / w / up / down 16-byte aligned.  Any N and any R; no workspace. */
+int drag_lora_merge_bf16(const void* w0, int64_t ldw0, void* w, int64_t ldw, int32_t N, int32_t K, const void* up, int32_t ldup,
+                         const void* down, int32_t lddown, const float* scale, int32_t R, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * drag_conv3x3_bf16 — 3x3 convolution as an implicit GEMM on the same MFMA main loop.
  * Replaces torch.nn.Conv2d(k=3) inside AutoencoderKL.encode/decode (Flux VAE; diffusers 0.33.1,
  * un-vendored; reached at the start/end of pipe(...) / pipe_fill(...):

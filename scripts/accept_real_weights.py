@@ -237,6 +237,19 @@ def _latent_recorder(store):
     return cb
 
 
+def _apply_loras(pipe, args):
+    """--lora: the same diffusers calls on either side (the reference's own pipeline, or the compat one, which merges the adapter into
+    the DiT's resident weights): load every file, then set the scales"""
+    from domain_rag_amd.lora import parse_lora_arg
+    specs = [parse_lora_arg(a) for a in (getattr(args, "lora", None) or [])]
+    names = []
+    for i, (path, _) in enumerate(specs):
+        names.append(f"accept_{i}")
+        pipe.load_lora_weights(os.path.dirname(path) or ".", weight_name=os.path.basename(path), adapter_name=names[-1])
+    if specs:
+        pipe.set_adapters(names, adapter_weights=[s for _, s in specs])
+
+
 def _ref_pipes(args, kind):
     """the reference's load_model() (batch_…:117-153 / outpainting_…:500-543) with the real diffusers / transformers"""
     import torch
@@ -254,6 +267,7 @@ def _ref_pipes(args, kind):
                                                 torch_dtype=dt).to(args.ref_device)
     else:
         pipe = FluxPipeline.from_pretrained(flux, text_encoder=None, text_encoder_2=None, torch_dtype=dt).to(args.ref_device)
+    _apply_loras(pipe, args)
     return prior, pipe, (te, te2, tok, tok2)
 
 
@@ -273,6 +287,7 @@ def _hip_pipes(args, kind, encoders):
         pipe.pipe.step_cache_warmup = getattr(args, "step_cache_warmup", None) or 0
     if getattr(args, "attention_precision", None):      # --attention-precision: the HIP side's DiT attention (flux.FluxTransformerHIP)
         pipe.pipe.tr.attention_precision = args.attention_precision
+    _apply_loras(pipe, args)                            # --lora: merged into the DiT's weights (flux.FluxTransformerHIP.load_lora)
     return prior, pipe
 
 
@@ -372,6 +387,9 @@ def main(argv=None) -> int:
                     help="with --step-cache: the first N steps compute (default: 0)")
     ap.add_argument("--attention-precision", choices=["bf16", "mxfp8"], default=None,
                     help="run the HIP stage-2 / stage-3 pipelines with this attention precision in the DiT (default: the process default, bf16)")
+    ap.add_argument("--lora", action="append", default=None, metavar="PATH[:SCALE]",
+                    help="load this LoRA adapter on both sides (diffusers' load_lora_weights + set_adapters) before stage 2 / 3; repeatable "
+                         "(default: none)")
     args = ap.parse_args(argv)
     sections = [s for s in args.sections.split(",") if s]
     bad = [s for s in sections if s not in SECTIONS]
@@ -391,6 +409,9 @@ def main(argv=None) -> int:
                 report[name] = getattr(args, name)
     if args.attention_precision == "mxfp8":
         report["attention_precision"] = args.attention_precision
+    if args.lora:
+        from domain_rag_amd.lora import parse_lora_arg
+        report["lora"] = [{"file": os.path.basename(p), "scale": s} for p, s in map(parse_lora_arg, args.lora)]
     if any(s in sections for s in ("stage2", "stage3")) and not args.target:
         report["missing"].append("--target <inpainted k-shot image>")
     if report["missing"]:
