@@ -22,7 +22,8 @@ import os
 
 import torch
 
-from . import ops
+from . import flux_layout, ops
+from .flux_layout import linear_locations      # noqa: F401
 from .flux_params import FluxConfig
 from .step_cache import (STEP_CACHE_DEFAULT, STEP_CACHE_MAX_RUN_DEFAULT, STEP_CACHE_ORDER_DEFAULT, STEP_CACHE_SCOPE_DEFAULT,      # noqa: F401
                          STEP_CACHE_SCOPES, STEP_CACHE_WARMUP_DEFAULT, StepCache, StepDecision, compact_pairs, forecast_coefficient,
@@ -75,43 +76,47 @@ def latent_image_ids(h: int, w: int) -> torch.Tensor:
     return ids.reshape(h * w, 3)
 
 
-def linear_locations(cfg: FluxConfig) -> dict:
-    """Where :class:`FluxTransformerHIP` keeps each Linear weight: every 2-D name of ``flux_params.param_shapes(cfg)`` ->
-    ``(holder, row0, rows)``.  A holder names one resident tensor: ``("w", name)`` = ``model.w[name]``, ``("double", i, key)`` /
-    ``("single", i, key)`` = ``model.double[i][key]`` / ``model.single[i][key]`` (the stacked ``wqkv`` / ``cwqkv`` / ``wqkvm`` hold
-    several names as row ranges), ``("mod_w",)`` = the stacked modulation matrix, whose row offsets are ``model.mod_off``'s.  A pure
-    function of the config (the constructor's layout, restated); LoRA adapters find their targets with it."""
-    D, F = cfg.dim, cfg.mlp_ratio * cfg.dim
-    loc: dict = {}
-    names = ["x_embedder", "context_embedder", "proj_out", "time_text_embed.timestep_embedder.linear_1",
-             "time_text_embed.timestep_embedder.linear_2", "time_text_embed.text_embedder.linear_1", "time_text_embed.text_embedder.linear_2"]
-    if cfg.guidance_embeds:
-        names += ["time_text_embed.guidance_embedder.linear_1", "time_text_embed.guidance_embedder.linear_2"]
-    rows_of = {"x_embedder": D, "context_embedder": D, "proj_out": cfg.out_channels}
-    for n in names:
-        loc[n + ".weight"] = (("w", n + ".weight"), 0, rows_of.get(n, D))
-    off = 0
-    for i in range(cfg.num_layers):
-        p = f"transformer_blocks.{i}."
-        for nm in ("norm1", "norm1_context"):
-            loc[p + nm + ".linear.weight"] = (("mod_w",), off, 6 * D)
-            off += 6 * D
-        for key, parts in (("wqkv", ("attn.to_q", "attn.to_k", "attn.to_v")), ("cwqkv", ("attn.add_q_proj", "attn.add_k_proj", "attn.add_v_proj"))):
-            for j, n in enumerate(parts):
-                loc[p + n + ".weight"] = (("double", i, key), j * D, D)
-        for key, n, rows in (("wo", "attn.to_out.0", D), ("cwo", "attn.to_add_out", D), ("w1", "ff.net.0.proj", F), ("w2", "ff.net.2", D),
-                             ("cw1", "ff_context.net.0.proj", F), ("cw2", "ff_context.net.2", D)):
-            loc[p + n + ".weight"] = (("double", i, key), 0, rows)
-    for i in range(cfg.num_single_layers):
-        p = f"single_transformer_blocks.{i}."
-        loc[p + "norm.linear.weight"] = (("mod_w",), off, 3 * D)
-        off += 3 * D
-        for j, n in enumerate(("attn.to_q", "attn.to_k", "attn.to_v")):
-            loc[p + n + ".weight"] = (("single", i, "wqkvm"), j * D, D)
-        loc[p + "proj_mlp.weight"] = (("single", i, "wqkvm"), 3 * D, F)
-        loc[p + "proj_out.weight"] = (("single", i, "wo"), 0, D)
-    loc["norm_out.linear.weight"] = (("mod_w",), off, 2 * D)
-    return loc
+class _Buffers:
+    """what a forward's launches address besides weights and inputs: the workspace and the RoPE tables with the keys they were made for,
+    and the two time buffers.  The model has one for the eager path; a captured graph, which bakes the addresses in, owns its own."""
+    def __init__(self):
+        self.ws_key = self.ws = self.rope_key = self.rope = self.t1000 = self.g1000 = None
+
+    def set_times(self, timestep, guidance, device) -> None:
+        """host fp32 [B] sigma / guidance scale -> persistent device buffers holding bf16(bf16(x) * 1000) as fp32
+        (diffusers: ``timestep.to(hidden_states.dtype) * 1000``)."""
+        B = timestep.numel()
+        if self.t1000 is None or self.t1000.numel() != B:
+            self.t1000 = torch.empty(B, dtype=torch.float32, device=device)
+            self.g1000 = torch.empty(B, dtype=torch.float32, device=device)
+        self.t1000.copy_((timestep.to(torch.bfloat16) * 1000).float())
+        if guidance is not None:
+            self.g1000.copy_((guidance.to(torch.bfloat16) * 1000).float())
+
+
+class _Rows:
+    """one row set of the joint buffers: ``per`` rows of every image from row ``first`` of its S on.  ``M`` rows in all; ``x`` / ``qkv`` /
+    ``attn``: the workspace buffers from the set's first row on; the set's row map in the spellings ``ops.layernorm`` (``ln``: reading x)
+    and ``ops.gemm`` take (``a_attn``: reading attn; ``c_x`` / ``c_qkv``: writing x / qkv)"""
+    def __init__(self, ws, nb, first, per, S, D):
+        self.M = nb * per
+        self.x, self.qkv, self.attn = (ws[k].view(-1)[first * ld:] if first else ws[k] for k, ld in (("x", D), ("qkv", 3 * D), ("attn", D)))
+        self.ln = dict(ldx=D, rows_per_batch=per, x_batch_stride=S * D)
+        self.a_attn = dict(a_rows_per_batch=per, a_batch_stride=S * D, lda=D)
+        self.c_x = dict(c_rows_per_batch=per, c_batch_stride=S * D, ldc=D)
+        self.c_qkv = dict(c_rows_per_batch=per, c_batch_stride=S * 3 * D, ldc=3 * D)
+
+
+class _Joint:
+    """the joint [nb, St + Si, .] activation buffers of a forward at batch ``nb`` (text rows first): the three row sets the launches address
+    (``img``, ``txt``, ``all``) and the dense scratch of the double blocks, image rows then text rows: the LayerNorm outputs ``nrm_img`` /
+    ``nrm_txt`` and the MLP hidden ``hid`` / ``hid_txt``.  Every row-map keyword of the forward comes from here."""
+    def __init__(self, ws, nb, St, Si, D, F):
+        self.nb, self.St, self.S = nb, St, St + Si
+        self.img, self.txt, self.all = _Rows(ws, nb, St, Si, self.S, D), _Rows(ws, nb, 0, St, self.S, D), _Rows(ws, nb, 0, self.S, self.S, D)
+        Mi, Mt = self.img.M, self.txt.M
+        nrm, self.hid = ws["nrm"].view(-1), ws["cat"].view(-1)
+        self.nrm_img, self.nrm_txt, self.hid_txt = nrm[: Mi * D], nrm[Mi * D: (Mi + Mt) * D], self.hid[Mi * F:]
 
 
 class FluxTransformerHIP:
@@ -123,74 +128,36 @@ class FluxTransformerHIP:
         if cfg.attention_head_dim != 128:
             raise ValueError("the HIP attention kernel is specialised for head_dim 128 (all FLUX.1 models)")
         self.cfg = cfg
-        self.device = torch.device(device)
-        D = cfg.dim
-        dev = self.device
+        self.device = dev = torch.device(device)
 
         def g(name):
             return params[name].to(dev, torch.bfloat16).contiguous()
 
-        def cat(names):
-            return torch.cat([params[n].to(dev, torch.bfloat16) for n in names], dim=0).contiguous()
+        def stack(names, suffix):      # (one member: the parameter itself when it is on the device in bf16 already, no copy)
+            return g(names[0] + suffix) if len(names) == 1 else torch.cat([params[n + suffix].to(dev, torch.bfloat16) for n in names], dim=0).contiguous()
 
-        self.w = {}
-        for n in ("x_embedder", "context_embedder", "proj_out",
-                  "time_text_embed.timestep_embedder.linear_1", "time_text_embed.timestep_embedder.linear_2",
-                  "time_text_embed.text_embedder.linear_1", "time_text_embed.text_embedder.linear_2"):
-            self.w[n + ".weight"], self.w[n + ".bias"] = g(n + ".weight"), g(n + ".bias")
-        if cfg.guidance_embeds:
-            for n in ("time_text_embed.guidance_embedder.linear_1", "time_text_embed.guidance_embedder.linear_2"):
-                self.w[n + ".weight"], self.w[n + ".bias"] = g(n + ".weight"), g(n + ".bias")
-
-        # ---- stacked modulation weights: [double i: norm1 (6D) | norm1_context (6D)]*L, [single: 3D]*Ls, norm_out 2D
-        mod_w, mod_b = [], []
-        self.mod_off = {}
-        off = 0
-        for i in range(cfg.num_layers):
-            for nm in ("norm1", "norm1_context"):
-                key = f"transformer_blocks.{i}.{nm}.linear"
-                mod_w.append(key + ".weight"); mod_b.append(key + ".bias")
-                self.mod_off[(i, nm)] = off
-                off += 6 * D
-        for i in range(cfg.num_single_layers):
-            key = f"single_transformer_blocks.{i}.norm.linear"
-            mod_w.append(key + ".weight"); mod_b.append(key + ".bias")
-            self.mod_off[("s", i)] = off
-            off += 3 * D
-        mod_w.append("norm_out.linear.weight"); mod_b.append("norm_out.linear.bias")
-        self.mod_off["out"] = off
-        off += 2 * D
-        self.mod_total = off
-        self.mod_w, self.mod_b = cat(mod_w), cat(mod_b)
-
-        self.double = []
-        for i in range(cfg.num_layers):
-            p = f"transformer_blocks.{i}."
-            self.double.append(dict(
-                wqkv=cat([p + "attn.to_q.weight", p + "attn.to_k.weight", p + "attn.to_v.weight"]),
-                bqkv=cat([p + "attn.to_q.bias", p + "attn.to_k.bias", p + "attn.to_v.bias"]),
-                cwqkv=cat([p + "attn.add_q_proj.weight", p + "attn.add_k_proj.weight", p + "attn.add_v_proj.weight"]),
-                cbqkv=cat([p + "attn.add_q_proj.bias", p + "attn.add_k_proj.bias", p + "attn.add_v_proj.bias"]),
-                nq=g(p + "attn.norm_q.weight"), nk=g(p + "attn.norm_k.weight"),
-                cnq=g(p + "attn.norm_added_q.weight"), cnk=g(p + "attn.norm_added_k.weight"),
-                wo=g(p + "attn.to_out.0.weight"), bo=g(p + "attn.to_out.0.bias"),
-                cwo=g(p + "attn.to_add_out.weight"), cbo=g(p + "attn.to_add_out.bias"),
-                w1=g(p + "ff.net.0.proj.weight"), b1=g(p + "ff.net.0.proj.bias"),
-                w2=g(p + "ff.net.2.weight"), b2=g(p + "ff.net.2.bias"),
-                cw1=g(p + "ff_context.net.0.proj.weight"), cb1=g(p + "ff_context.net.0.proj.bias"),
-                cw2=g(p + "ff_context.net.2.weight"), cb2=g(p + "ff_context.net.2.bias")))
-        self.single = []
-        for i in range(cfg.num_single_layers):
-            p = f"single_transformer_blocks.{i}."
-            # to_q | to_k | to_v | proj_mlp stacked in one weight: either two GEMMs over its row ranges (default) or ONE two-destination
-            # launch ($DRAG_QKV_MLP_FUSED=1: q/k/v into the qkv buffer, the GELU'd MLP hidden into the [attn | mlp] buffer)
-            self.single.append(dict(
-                wqkvm=cat([p + "attn.to_q.weight", p + "attn.to_k.weight", p + "attn.to_v.weight", p + "proj_mlp.weight"]),
-                bqkvm=cat([p + "attn.to_q.bias", p + "attn.to_k.bias", p + "attn.to_v.bias", p + "proj_mlp.bias"]),
-                nq=g(p + "attn.norm_q.weight"), nk=g(p + "attn.norm_k.weight"),
-                wo=g(p + "proj_out.weight"), bo=g(p + "proj_out.bias")))
-        self._ws_key = None
-        self._rope_key = None
+        # ---- the resident tensors, by flux_layout's tables
+        self.w = {n + sfx: g(n + sfx) for n in flux_layout.top_linears(cfg) for sfx in (".weight", ".bias")}
+        mod = flux_layout.modulation(cfg)
+        self.mod_w, self.mod_b = stack([n for _, n in mod], ".weight"), stack([n for _, n in mod], ".bias")
+        self.mod_off, self.mod_total = {}, 0
+        for key, n in mod:
+            self.mod_off[key] = self.mod_total
+            self.mod_total += params[n + ".weight"].shape[0]
+        for kind, prefix, count, linears, norms in flux_layout.BLOCKS:
+            blocks = []
+            for i in range(getattr(cfg, count)):
+                p = f"{prefix}.{i}."
+                blk = {key: g(p + n + ".weight") for key, n in norms.items()}
+                for key, (bias_key, members) in linears.items():
+                    blk[key], blk[bias_key] = stack([p + m for m in members], ".weight"), stack([p + m for m in members], ".bias")
+                blocks.append(blk)
+            setattr(self, kind, blocks)                      # self.double, self.single
+        # the two launch ranges of a single block's wqkvm, q|k|v and proj_mlp: it splits where proj_mlp begins
+        _, lo, rows = linear_locations(cfg).get("single_transformer_blocks.0.proj_mlp.weight", (None, 0, 0))
+        self._qkvm_rows = ((0, lo), (lo, lo + rows))
+        self._buf = _Buffers()           # the eager path's; a captured graph owns its own (forward_graphed)
+        self._graphs: dict = {}
         self._mx_ready = False
         self._loras: dict = {}           # name -> {"adapter", "scale"}: the active LoRA adapters, in load order
         self._pristine: dict = {}        # holder -> a copy of the resident tensor as built, while an adapter touches it
@@ -200,9 +167,6 @@ class FluxTransformerHIP:
     # ------------------------------------------------------------------ MXFP8 mode
     # What moves (blocks only): both streams' to_q|k|v, the attention out-projections, ff up (+GELU) and ff down, the single blocks'
     # q|k|v + proj_mlp and proj_out.  Embedders, the stacked modulation GEMV, the final proj_out and everything outside the DiT stay bf16.
-    _MX_DOUBLE = ("wqkv", "cwqkv", "wo", "cwo", "w1", "cw1", "w2", "cw2")
-    _MX_SINGLE = ("wqkvm", "wo")
-
     @property
     def linear_precision(self) -> str:
         return self._linear_precision
@@ -214,13 +178,12 @@ class FluxTransformerHIP:
         if value == "mxfp8" and not self._mx_ready:
             # the weights' MX copies, by the kernel that quantises the activations (rows are quantised one by one: stacking changes nothing)
             # (a weight none of whose launch shapes moves gets no copy)
-            D, F = self.cfg.dim, self.cfg.mlp_ratio * self.cfg.dim
             self._linear_precision = value
-            for blocks, keys in ((self.double, self._MX_DOUBLE), (self.single, self._MX_SINGLE)):
-                for blk in blocks:
-                    for k in keys:
+            for kind, _, _, linears, _ in flux_layout.BLOCKS:
+                for blk in getattr(self, kind):
+                    for k in linears:
                         N, K = blk[k].shape
-                        if self._mx_moves(N, K) if k != "wqkvm" else (self._mx_moves(3 * D, D) or self._mx_moves(F, D)):
+                        if any(self._mx_moves(hi - lo, K) for lo, hi in (self._qkvm_rows if k == "wqkvm" else ((0, N),))):
                             blk[k + "@mx"] = ops.quantize_mxfp8(blk[k])
             self._mx_ready = True
         self._linear_precision = value
@@ -244,8 +207,7 @@ class FluxTransformerHIP:
         """one block's attention over ws["qkv"] into ``out`` (rows of ``ld_o``).  "mxfp8": the MX prep pass (qkv stays as projected) and the
         MX kernel on the workspace's images (_SEPARATE_QPREP is a switch of the bf16 route and is ignored); a shape that kernel refuses
         by contract takes the bf16 launches, and the launch record shows them.  "bf16": k prepared in place + V^T, q on the kernel's load."""
-        cfg = self.cfg
-        D, H = cfg.dim, cfg.num_attention_heads
+        D, H = self.cfg.dim, self.cfg.num_attention_heads
         qkv, vt = ws["qkv"], ws["vt"]
         if self._attention_precision == "mxfp8" and ops.attention_mxfp8_supported(nb, S, H):
             ops.qkv_prep_mxfp8(qkv, ws["mxa"], wq_txt, wk_txt, wq_img, wk_img, cos, sin, nb, S, H, 3 * D, St)
@@ -267,24 +229,34 @@ class FluxTransformerHIP:
         out = (ws["mxq"][row0 * K:], ws["mxs"][row0 * (K // 32):])
         return ops.quantize_mxfp8(a, M=M, K=K, lda=lda, rows_per_batch=rows_per_batch, batch_stride=batch_stride, out=out)
 
-    def _mx_gemm(self, ws, d, wmx, row0=0, qa=None):
-        """one Linear given as ``ops.gemm`` keywords (``a``, ``out`` included) on the MX route: quantise its input unless ``qa`` has it"""
-        M, K = d["M"], wmx[0].shape[1]
-        if qa is None:
-            qa = self._mx_quant(ws, d["a"], M, K, d.get("lda", K), d.get("a_rows_per_batch", 0), d.get("a_batch_stride", 0), row0)
-        ops.gemm_mxfp8(qa[0], qa[1], wmx[0], wmx[1], d["out"], bias=d.get("bias"), act=d.get("act", ops.ACT_NONE), act_n0=d.get("act_n0", 0),
-                       gate=d.get("gate"), resid=d.get("resid"), M=M, c_rows_per_batch=d.get("c_rows_per_batch", 0),
-                       c_batch_stride=d.get("c_batch_stride", 0), ldc=d["ldc"], ldg=d.get("ldg", 0))
+    def _has_mx(self, blk, key) -> bool:
+        """does a launch shape of this weight run on the MX route (decided at set-up: it has a copy)?"""
+        return self._linear_precision == "mxfp8" and key + "@mx" in blk
+
+    def _linear(self, ws, blk, key, kw, rows=None, qa=None, row0=0):
+        """THE route of a block Linear: ``kw`` are its ``ops.gemm`` keywords (``a``, ``out`` included; ``bias`` the whole bias of ``blk[key]``),
+        ``rows`` a row range (lo, hi) of a stacked weight.  bf16: that GEMM.  A shape that moves in "mxfp8" mode: quantise ``a`` into the
+        workspace's scratch from dense row ``row0`` on (unless ``qa`` holds it already) + the MX GEMM with the same epilogue keywords."""
+        kw, w = dict(kw), blk[key]
+        lo, hi = rows or (0, w.shape[0])
+        a, K = kw.pop("a"), w.shape[1]
+        if rows:
+            kw["bias"] = kw["bias"][lo:hi]
+        if not self._mx_moves(hi - lo, K):
+            return ops.gemm(a, w[lo:hi] if rows else w, **kw)
+        lda, per, stride = kw.pop("lda", K), kw.pop("a_rows_per_batch", 0), kw.pop("a_batch_stride", 0)
+        qa = qa or self._mx_quant(ws, a, kw["M"], K, lda, per, stride, row0)
+        wq, wscale = blk[key + "@mx"]
+        return ops.gemm_mxfp8(qa[0], qa[1], wq[lo:hi] if rows else wq, wscale[lo:hi] if rows else wscale, kw.pop("out"), **kw)
 
     def _pair(self, ws, blk, key1, d1, key2, d2):
-        """a double block's image / text Linear pair: ``ops.gemm_pair`` in bf16, two quantise + GEMM launches each on the MX route (there
-        is no MX pair form); the text rows' scratch follows the image rows'"""
-        if not self._mx_moves(*blk[key1].shape):
-            d1 = dict(d1, w=blk[key1]); d2 = dict(d2, w=blk[key2])
-            ops.gemm_pair(d1, d2)
-            return
-        self._mx_gemm(ws, d1, blk[key1 + "@mx"])
-        self._mx_gemm(ws, d2, blk[key2 + "@mx"], row0=d1["M"])
+        """a double block's image / text Linear pair (same N and K): ``ops.gemm_pair`` in bf16, two calls of the route where the shape moves
+        (there is no MX pair form); the text rows' scratch follows the image rows'"""
+        if self._has_mx(blk, key1):
+            self._linear(ws, blk, key1, d1)
+            self._linear(ws, blk, key2, d2, row0=d1["M"])
+        else:
+            ops.gemm_pair(dict(d1, w=blk[key1]), dict(d2, w=blk[key2]))
 
     # ------------------------------------------------------------------ LoRA adapters
     # Adapters are MERGED into the resident bf16 weights, in place (ops.lora_merge; the rule: lora.py): a forward with an adapter launches
@@ -295,9 +267,7 @@ class FluxTransformerHIP:
     def _holder(self, holder):
         if holder[0] == "w":
             return self.w[holder[1]]
-        if holder[0] == "mod_w":
-            return self.mod_w
-        return (self.double if holder[0] == "double" else self.single)[holder[1]][holder[2]]
+        return self.mod_w if holder[0] == "mod_w" else getattr(self, holder[0])[holder[1]][holder[2]]
 
     @property
     def loras(self) -> list:
@@ -385,7 +355,7 @@ class FluxTransformerHIP:
             ops.lora_merge(w0[row0: row0 + rows], w[row0: row0 + rows], up, down, scale.to(dev))
         for holder in changed:
             if holder[0] in ("double", "single"):
-                blk = (self.double if holder[0] == "double" else self.single)[holder[1]]
+                blk = getattr(self, holder[0])[holder[1]]
                 if holder[2] + "@mx" in blk:                # the MX copy follows, into the buffers it has
                     ops.quantize_mxfp8(blk[holder[2]], out=blk[holder[2] + "@mx"])
             if holder not in active_holders:
@@ -394,8 +364,8 @@ class FluxTransformerHIP:
     # ------------------------------------------------------------------ workspaces
     def _workspace(self, B, St, Si):
         key = (B, St, Si)
-        if self._ws_key == key:
-            return self._ws
+        if self._buf.ws_key == key:
+            return self._buf.ws
         cfg, dev = self.cfg, self.device
         D, S, H = cfg.dim, St + Si, cfg.num_attention_heads
         F = cfg.mlp_ratio * D
@@ -411,7 +381,7 @@ class FluxTransformerHIP:
             mod=torch.empty((B, self.mod_total), **bf),
             out=torch.empty((B * Si, cfg.out_channels), **bf),
         )
-        self._ws_key, self._ws = key, ws
+        self._buf.ws_key, self._buf.ws = key, ws
         return ws
 
     @staticmethod
@@ -421,34 +391,22 @@ class FluxTransformerHIP:
                 hash(img_ids.cpu().float().contiguous().numpy().tobytes()))
 
     def _rope(self, txt_ids, img_ids):
-        key = self._ids_key(txt_ids, img_ids)
-        if self._rope_key != key:
+        key, buf = self._ids_key(txt_ids, img_ids), self._buf
+        if buf.rope_key != key:
             cos, sin = rope_tables(torch.cat([txt_ids.cpu().float(), img_ids.cpu().float()], dim=0), self.cfg.axes_dims_rope)
-            self._rope_cs = (cos.to(self.device), sin.to(self.device))
-            self._rope_key = key
-        return self._rope_cs
+            buf.rope_key, buf.rope = key, (cos.to(self.device), sin.to(self.device))
+        return buf.rope
 
     # ------------------------------------------------------------------ pieces
-    def _set_times(self, timestep, guidance):
-        """host fp32 [B] sigma / guidance scale -> persistent device buffers holding bf16(bf16(x) * 1000) as fp32
-        (diffusers: ``timestep.to(hidden_states.dtype) * 1000``)."""
-        B = timestep.numel()
-        if getattr(self, "_t1000", None) is None or self._t1000.numel() != B:
-            self._t1000 = torch.empty(B, dtype=torch.float32, device=self.device)
-            self._g1000 = torch.empty(B, dtype=torch.float32, device=self.device)
-        self._t1000.copy_((timestep.to(torch.bfloat16) * 1000).float())
-        if guidance is not None:
-            self._g1000.copy_((guidance.to(torch.bfloat16) * 1000).float())
-
     def _temb(self, pooled, use_guidance: bool):
-        """CombinedTimestep(Guidance)TextProjEmbeddings on the times held in the device buffers (see _set_times)."""
+        """CombinedTimestep(Guidance)TextProjEmbeddings on the times held in the device buffers (_Buffers.set_times)."""
         w = self.w
-        tp = ops.timestep_embedding(self._t1000, 256)
+        tp = ops.timestep_embedding(self._buf.t1000, 256)
         pre = "time_text_embed."
         h = ops.gemm(tp, w[pre + "timestep_embedder.linear_1.weight"], bias=w[pre + "timestep_embedder.linear_1.bias"], act=ops.ACT_SILU)
         emb = ops.gemm(h, w[pre + "timestep_embedder.linear_2.weight"], bias=w[pre + "timestep_embedder.linear_2.bias"])
         if use_guidance:
-            gp = ops.timestep_embedding(self._g1000, 256)
+            gp = ops.timestep_embedding(self._buf.g1000, 256)
             h = ops.gemm(gp, w[pre + "guidance_embedder.linear_1.weight"], bias=w[pre + "guidance_embedder.linear_1.bias"], act=ops.ACT_SILU)
             emb = ops.gemm(h, w[pre + "guidance_embedder.linear_2.weight"], bias=w[pre + "guidance_embedder.linear_2.bias"], resid=emb)
         h = ops.gemm(pooled, w[pre + "text_embedder.linear_1.weight"], bias=w[pre + "text_embedder.linear_1.bias"], act=ops.ACT_SILU)
@@ -457,95 +415,63 @@ class FluxTransformerHIP:
     # ------------------------------------------------------------------ blocks
     # Every workspace buffer is batch-leading or flat scratch, so its first ``nb`` slots are the workspace of a batch-``nb`` forward: the
     # blocks take the batch size they run at (B, or under a step cache of scope "image" the number of computing images).
-    def _double_block(self, ws, i, nb, St, Si, cos, sin, taps):
+    def _double_block(self, ws, i, j, cos, sin, taps):
         cfg = self.cfg
-        D, H, S, LM = cfg.dim, cfg.num_attention_heads, St + Si, self.mod_total
+        D, LM = cfg.dim, self.mod_total
         F = cfg.mlp_ratio * D
-        Mi, Mt = nb * Si, nb * St
-        x, nrm, qkv, vt, attn, modv = ws["x"], ws["nrm"], ws["qkv"], ws["vt"], ws["attn"], ws["mod"].view(-1)
-        x_img = x.view(-1)[St * D:]          # joint buffer, image rows of batch 0 onwards
-        nrm_img = nrm.view(-1)[: Mi * D]
-        nrm_txt = nrm.view(-1)[Mi * D: (Mi + Mt) * D]
-        qkv_img = qkv.view(-1)[St * 3 * D:]
-        attn_img = attn.view(-1)[St * D:]
-        hid = ws["cat"].view(-1)              # MLP hidden scratch for double blocks: image rows, then text rows
-        hid_txt = hid[Mi * F:]
+        img, txt, modv = j.img, j.txt, ws["mod"].view(-1)
         scale = 1.0 / math.sqrt(cfg.attention_head_dim)
         blk = self.double[i]
         mo, cmo = self.mod_off[(i, "norm1")], self.mod_off[(i, "norm1_context")]
         # chunk order: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
-        ops.layernorm(x_img, nrm_img, Mi, D, scale=modv[mo + D:], shift=modv[mo:], ldx=D, rows_per_batch=Si,
-                      x_batch_stride=S * D, ld_mod=LM)
-        ops.layernorm(x, nrm_txt, Mt, D, scale=modv[cmo + D:], shift=modv[cmo:], ldx=D, rows_per_batch=St,
-                      x_batch_stride=S * D, ld_mod=LM)
+        ops.layernorm(img.x, j.nrm_img, img.M, D, scale=modv[mo + D:], shift=modv[mo:], ld_mod=LM, **img.ln)
+        ops.layernorm(txt.x, j.nrm_txt, txt.M, D, scale=modv[cmo + D:], shift=modv[cmo:], ld_mod=LM, **txt.ln)
         # the image-stream and text-stream Linears of a pair share N and K: one launch when they are small alone (ops.gemm_pair)
-        self._pair(ws, blk, "wqkv", dict(a=nrm_img, out=qkv_img, bias=blk["bqkv"], M=Mi, lda=D, c_rows_per_batch=Si,
-                                         c_batch_stride=S * 3 * D, ldc=3 * D),
-                   "cwqkv", dict(a=nrm_txt, out=qkv, bias=blk["cbqkv"], M=Mt, lda=D, c_rows_per_batch=St,
-                                 c_batch_stride=S * 3 * D, ldc=3 * D))
-        self._attention(ws, nb, S, St, blk["cnq"], blk["cnk"], blk["nq"], blk["nk"], cos, sin, attn, D, scale)
-        self._pair(ws, blk, "wo", dict(a=attn_img, out=x_img, bias=blk["bo"], M=Mi, a_rows_per_batch=Si, a_batch_stride=S * D,
-                                       lda=D, c_rows_per_batch=Si, c_batch_stride=S * D, ldc=D, gate=modv[mo + 2 * D:], resid=x_img, ldg=LM),
-                   "cwo", dict(a=attn, out=x, bias=blk["cbo"], M=Mt, a_rows_per_batch=St, a_batch_stride=S * D,
-                               lda=D, c_rows_per_batch=St, c_batch_stride=S * D, ldc=D, gate=modv[cmo + 2 * D:], resid=x, ldg=LM))
+        self._pair(ws, blk, "wqkv", dict(a=j.nrm_img, out=img.qkv, bias=blk["bqkv"], M=img.M, lda=D, **img.c_qkv),
+                   "cwqkv", dict(a=j.nrm_txt, out=txt.qkv, bias=blk["cbqkv"], M=txt.M, lda=D, **txt.c_qkv))
+        self._attention(ws, j.nb, j.S, j.St, blk["cnq"], blk["cnk"], blk["nq"], blk["nk"], cos, sin, ws["attn"], D, scale)
+        self._pair(ws, blk, "wo", dict(a=img.attn, out=img.x, bias=blk["bo"], M=img.M, gate=modv[mo + 2 * D:], resid=img.x, ldg=LM, **img.a_attn, **img.c_x),
+                   "cwo", dict(a=txt.attn, out=txt.x, bias=blk["cbo"], M=txt.M, gate=modv[cmo + 2 * D:], resid=txt.x, ldg=LM, **txt.a_attn, **txt.c_x))
         # MLPs (the two streams are independent: both LayerNorms, both up-projections, both down-projections)
-        ops.layernorm(x_img, nrm_img, Mi, D, scale=modv[mo + 4 * D:], shift=modv[mo + 3 * D:], ldx=D,
-                      rows_per_batch=Si, x_batch_stride=S * D, ld_mod=LM)
-        ops.layernorm(x, nrm_txt, Mt, D, scale=modv[cmo + 4 * D:], shift=modv[cmo + 3 * D:], ldx=D,
-                      rows_per_batch=St, x_batch_stride=S * D, ld_mod=LM)
-        self._pair(ws, blk, "w1", dict(a=nrm_img, out=hid, bias=blk["b1"], act=ops.ACT_GELU_TANH, M=Mi, lda=D, ldc=F),
-                   "cw1", dict(a=nrm_txt, out=hid_txt, bias=blk["cb1"], act=ops.ACT_GELU_TANH, M=Mt, lda=D, ldc=F))
-        self._pair(ws, blk, "w2", dict(a=hid, out=x_img, bias=blk["b2"], M=Mi, lda=F, c_rows_per_batch=Si,
-                                       c_batch_stride=S * D, ldc=D, gate=modv[mo + 5 * D:], resid=x_img, ldg=LM),
-                   "cw2", dict(a=hid_txt, out=x, bias=blk["cb2"], M=Mt, lda=F, c_rows_per_batch=St,
-                               c_batch_stride=S * D, ldc=D, gate=modv[cmo + 5 * D:], resid=x, ldg=LM))
+        ops.layernorm(img.x, j.nrm_img, img.M, D, scale=modv[mo + 4 * D:], shift=modv[mo + 3 * D:], ld_mod=LM, **img.ln)
+        ops.layernorm(txt.x, j.nrm_txt, txt.M, D, scale=modv[cmo + 4 * D:], shift=modv[cmo + 3 * D:], ld_mod=LM, **txt.ln)
+        self._pair(ws, blk, "w1", dict(a=j.nrm_img, out=j.hid, bias=blk["b1"], act=ops.ACT_GELU_TANH, M=img.M, lda=D, ldc=F),
+                   "cw1", dict(a=j.nrm_txt, out=j.hid_txt, bias=blk["cb1"], act=ops.ACT_GELU_TANH, M=txt.M, lda=D, ldc=F))
+        self._pair(ws, blk, "w2", dict(a=j.hid, out=img.x, bias=blk["b2"], M=img.M, lda=F, gate=modv[mo + 5 * D:], resid=img.x, ldg=LM, **img.c_x),
+                   "cw2", dict(a=j.hid_txt, out=txt.x, bias=blk["cb2"], M=txt.M, lda=F, gate=modv[cmo + 5 * D:], resid=txt.x, ldg=LM, **txt.c_x))
         if taps is not None:
-            taps[f"double.{i}"] = x[:nb].clone()
+            taps[f"double.{i}"] = ws["x"][:j.nb].clone()
 
-    def _blocks_after_first(self, ws, nb, St, Si, cos, sin, taps):
-        """double blocks 1... and the single blocks on the first ``nb`` slots of the workspace"""
+    def _blocks_after_first(self, ws, j, cos, sin, taps):
+        """double blocks 1... and the single blocks on the first ``j.nb`` slots of the workspace"""
         cfg = self.cfg
-        D, H, S, LM = cfg.dim, cfg.num_attention_heads, St + Si, self.mod_total
+        D, LM, M = cfg.dim, self.mod_total, j.all.M
         F = cfg.mlp_ratio * D
-        M = nb * S
-        x, nrm, qkv, vt, catb, modv = ws["x"], ws["nrm"], ws["qkv"], ws["vt"], ws["cat"], ws["mod"].view(-1)
+        x, nrm, qkv, catb, modv = ws["x"], ws["nrm"], ws["qkv"], ws["cat"], ws["mod"].view(-1)
         scale = 1.0 / math.sqrt(cfg.attention_head_dim)
         for i in range(1, len(self.double)):
-            self._double_block(ws, i, nb, St, Si, cos, sin, taps)
+            self._double_block(ws, i, j, cos, sin, taps)
 
         cat_mlp = catb.view(-1)[D:]
         fused_qkv_mlp = (3 * D) % 256 == 0 and (_FUSED_QKV_MLP if _FUSED_QKV_MLP is not None else
                                                 ops.gemm_cost(M, 3 * D + F, D) * 10 <= (ops.gemm_cost(M, 3 * D, D) + ops.gemm_cost(M, F, D)) * 9)
-        mx_qkv, mx_mlp, mx_out = self._mx_moves(3 * D, D), self._mx_moves(F, D), self._mx_moves(D, D + F)
         for i, blk in enumerate(self.single):
             mo = self.mod_off[("s", i)]      # shift, scale, gate
-            ops.layernorm(x, nrm, M, D, scale=modv[mo + D:], shift=modv[mo:], ldx=D, ld_mod=LM, rows_per_batch=S,
-                          x_batch_stride=S * D)
-            if mx_qkv or mx_mlp:
-                # one quantisation of the modulated LayerNorm output serves q|k|v and proj_mlp: two launches over the stacked weight's row
-                # ranges (a range whose shape stays on bf16 takes the bf16 GEMM)
-                qa = self._mx_quant(ws, nrm, M, D, D)
-                wq, wsc = blk["wqkvm@mx"]
-                for moves, lo, hi, dst, ldd, act_ in ((mx_qkv, 0, 3 * D, qkv, 3 * D, ops.ACT_NONE), (mx_mlp, 3 * D, 3 * D + F, cat_mlp, D + F, ops.ACT_GELU_TANH)):
-                    if moves:
-                        ops.gemm_mxfp8(qa[0], qa[1], wq[lo:hi], wsc[lo:hi], dst, bias=blk["bqkvm"][lo:hi], act=act_, M=M, ldc=ldd)
-                    else:
-                        ops.gemm(nrm, blk["wqkvm"][lo:hi], out=dst, bias=blk["bqkvm"][lo:hi], act=act_, M=M, lda=D, ldc=ldd)
-            elif fused_qkv_mlp:
-                ops.gemm(nrm, blk["wqkvm"], out=qkv, bias=blk["bqkvm"], act=ops.ACT_GELU_TANH, act_n0=3 * D, M=M, lda=D, ldc=3 * D,
-                         out2=cat_mlp, ldc2=D + F, n_split=3 * D)
-            else:       # (test-sized widths whose q|k|v block does not end on a tile boundary)
-                ops.gemm(nrm, blk["wqkvm"][: 3 * D], out=qkv, bias=blk["bqkvm"][: 3 * D], M=M, lda=D, ldc=3 * D)
-                ops.gemm(nrm, blk["wqkvm"][3 * D:], out=cat_mlp, bias=blk["bqkvm"][3 * D:], act=ops.ACT_GELU_TANH, M=M, lda=D, ldc=D + F)
-            self._attention(ws, nb, S, 0, blk["nq"], blk["nk"], blk["nq"], blk["nk"], cos, sin, catb, D + F, scale)
-            proj = dict(a=catb, out=x, bias=blk["bo"], M=M, lda=D + F, c_rows_per_batch=S, c_batch_stride=S * D,
-                        ldc=D, gate=modv[mo + 2 * D:], resid=x, ldg=LM)
-            if mx_out:
-                self._mx_gemm(ws, proj, blk["wo@mx"])
+            ops.layernorm(x, nrm, M, D, scale=modv[mo + D:], shift=modv[mo:], ld_mod=LM, **j.all.ln)
+            lin = dict(a=nrm, bias=blk["bqkvm"], M=M, lda=D)
+            mx = self._has_mx(blk, "wqkvm")
+            if fused_qkv_mlp and not mx:
+                ops.gemm(w=blk["wqkvm"], out=qkv, ldc=3 * D, act=ops.ACT_GELU_TANH, act_n0=3 * D, out2=cat_mlp, ldc2=D + F, n_split=3 * D, **lin)
             else:
-                ops.gemm(proj.pop("a"), blk["wo"], **proj)
+                # two launches over the stacked weight's row ranges (test-sized widths whose q|k|v block does not end on a tile boundary; "mxfp8":
+                # ONE quantisation of the modulated LayerNorm output serves both, and a range whose shape stays on bf16 takes the bf16 GEMM)
+                qa = self._mx_quant(ws, nrm, M, D, D) if mx else None
+                self._linear(ws, blk, "wqkvm", dict(lin, out=qkv, ldc=3 * D), self._qkvm_rows[0], qa)
+                self._linear(ws, blk, "wqkvm", dict(lin, out=cat_mlp, act=ops.ACT_GELU_TANH, ldc=D + F), self._qkvm_rows[1], qa)
+            self._attention(ws, j.nb, j.S, 0, blk["nq"], blk["nk"], blk["nq"], blk["nk"], cos, sin, catb, D + F, scale)
+            self._linear(ws, blk, "wo", dict(a=catb, out=x, bias=blk["bo"], M=M, lda=D + F, gate=modv[mo + 2 * D:], resid=x, ldg=LM, **j.all.c_x))
             if taps is not None:
-                taps[f"single.{i}"] = x[:nb].clone()
+                taps[f"single.{i}"] = x[:j.nb].clone()
 
     def forward(self, hidden, enc, pooled, timestep, img_ids, txt_ids, guidance=None, taps: dict | None = None,
                 cache: StepCache | None = None):
@@ -563,8 +489,8 @@ class FluxTransformerHIP:
         St = enc.shape[1]
         S = St + Si
         ws = self._workspace(B, St, Si)
-        x, nrm, mod = ws["x"], ws["nrm"], ws["mod"]
-        if "mxq" not in ws and any(self._mx_moves(n, k) for n, k in ((3 * D, D), (D, D), (F, D), (D, F), (D, D + F))):
+        x, mod = ws["x"], ws["mod"]
+        if "mxq" not in ws and self._linear_precision == "mxfp8" and any(k.endswith("@mx") for blk in self.double + self.single for k in blk):
             # the widest Linear input (the single blocks' [attn | mlp], D + F columns) as e4m3 bytes + its e8m0 scales
             ws["mxq"] = torch.empty(B * S * (D + F), dtype=torch.uint8, device=self.device)
             ws["mxs"] = torch.empty(B * S * (D + F) // 32, dtype=torch.uint8, device=self.device)
@@ -572,48 +498,42 @@ class FluxTransformerHIP:
             ws["mxa"] = ops.attention_mxfp8_images(B, S, cfg.num_attention_heads, self.device)      # the six MXFP8 attention images
         cos, sin = self._rope(txt_ids, img_ids)
         hidden = hidden.contiguous(); enc = enc.contiguous(); pooled = pooled.contiguous()
-        Mi, Mt = B * Si, B * St
-        x_img = x.view(-1)[St * D:]          # joint buffer, image rows of batch 0 onwards
+        j = _Joint(ws, B, St, Si, D, F)
+        img, txt = j.img, j.txt
 
         # embedders write straight into the joint buffer
-        ops.gemm(hidden.view(Mi, -1), self.w["x_embedder.weight"], out=x_img, bias=self.w["x_embedder.bias"], M=Mi,
-                 c_rows_per_batch=Si, c_batch_stride=S * D, ldc=D)
-        ops.gemm(enc.view(Mt, -1), self.w["context_embedder.weight"], out=x, bias=self.w["context_embedder.bias"], M=Mt,
-                 c_rows_per_batch=St, c_batch_stride=S * D, ldc=D)
+        ops.gemm(hidden.view(img.M, -1), self.w["x_embedder.weight"], out=img.x, bias=self.w["x_embedder.bias"], M=img.M, **img.c_x)
+        ops.gemm(enc.view(txt.M, -1), self.w["context_embedder.weight"], out=txt.x, bias=self.w["context_embedder.bias"], M=txt.M, **txt.c_x)
         if cfg.guidance_embeds and guidance is None:
             raise ValueError("this model has a guidance embedding: pass guidance")
         times = None                  # the host timesteps, for a step cache of order 1
         if timestep is not None:      # eager call: refresh the device-side times (a replayed graph gets them from forward_graphed)
             t_host = torch.as_tensor(timestep, dtype=torch.float32).cpu().reshape(-1)
-            self._set_times(t_host, None if guidance is None else torch.as_tensor(guidance, dtype=torch.float32).cpu().reshape(-1))
+            self._buf.set_times(t_host, None if guidance is None else torch.as_tensor(guidance, dtype=torch.float32).cpu().reshape(-1), self.device)
             if cache is not None:
                 times = t_host.tolist()
         temb = self._temb(pooled, cfg.guidance_embeds)
         st = ops.act(temb, ops.ACT_SILU)
         ops.gemm(st, self.mod_w, out=mod, bias=self.mod_b)          # every block's modulation in one GEMM
         modv = mod.view(-1)
-        LM = self.mod_total
         if taps is not None:
             taps["temb"] = temb.clone()
             taps["x_embed"] = x[:, St:].clone(); taps["ctx_embed"] = x[:, :St].clone()
 
-        nrm_img = nrm.view(-1)[: Mi * D]
         nb = B      # the batch size blocks 1... run at: under a step cache 0 on a reused step, the number of computing images on a mixed one
         if self.double:
             if cache is not None:
                 cache.before_first_block(x, B, St, Si, D, self._precision_key, self.device)
-            self._double_block(ws, 0, B, St, Si, cos, sin, taps)
+            self._double_block(ws, 0, j, cos, sin, taps)
             if cache is not None:
                 nb = cache.after_first_block(x, mod, B, St, Si, D, taps, times=times)
         if nb:
-            self._blocks_after_first(ws, nb, St, Si, cos, sin, taps)
+            self._blocks_after_first(ws, j if nb == B else _Joint(ws, nb, St, Si, D, F), cos, sin, taps)
         if cache is not None:
             cache.after_last_block(x, mod, B, St, Si, D)
         mo = self.mod_off["out"]             # AdaLayerNormContinuous: scale, shift
-        ops.layernorm(x_img, nrm_img, Mi, D, scale=modv[mo:], shift=modv[mo + D:], ldx=D, rows_per_batch=Si,
-                      x_batch_stride=S * D, ld_mod=LM)
-        ops.gemm(nrm_img, self.w["proj_out.weight"], out=ws["out"], bias=self.w["proj_out.bias"], M=Mi, lda=D,
-                 ldc=cfg.out_channels)
+        ops.layernorm(img.x, j.nrm_img, img.M, D, scale=modv[mo:], shift=modv[mo + D:], ld_mod=self.mod_total, **img.ln)
+        ops.gemm(j.nrm_img, self.w["proj_out.weight"], out=ws["out"], bias=self.w["proj_out.bias"], M=img.M, lda=D, ldc=cfg.out_channels)
         return ws["out"].view(B, Si, cfg.out_channels)
 
     # ------------------------------------------------------------------ hipGraph replay
@@ -636,31 +556,24 @@ class FluxTransformerHIP:
         rope_key = self._ids_key(txt_ids, img_ids)
         key = (hidden.data_ptr(), enc.data_ptr(), pooled.data_ptr(), tuple(hidden.shape), tuple(enc.shape), tuple(pooled.shape),
                guidance is None, rope_key) + self._precision_key
-        graphs = self.__dict__.setdefault("_graphs", {})
+        graphs = self._graphs
         ent = graphs.pop(key, None)
         if ent is None:
             while len(graphs) >= self.MAX_GRAPHS:
                 graphs.pop(next(iter(graphs)))                 # least recently used: drops its graph, workspace and tables
             # private buffers for this capture: nothing the eager path (or another graph) will ever reallocate
-            self._ws_key = self._rope_key = None
-            self._t1000 = self._g1000 = None
-            self._set_times(t, g)
-            rope = self._rope(txt_ids, img_ids)              # host-side table build + upload happen outside capture
-            ws = self._workspace(hidden.shape[0], enc.shape[1], hidden.shape[1])
-            self.forward(hidden, enc, pooled, None, img_ids, txt_ids, g)   # warm-up: allocates every temporary
+            self._buf = buf = _Buffers()
+            buf.set_times(t, g, self.device)
+            self._rope(txt_ids, img_ids)                     # host-side table build + upload happen outside capture
+            self.forward(hidden, enc, pooled, None, img_ids, txt_ids, g)   # warm-up: allocates the workspace and every temporary
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 out = self.forward(hidden, enc, pooled, None, img_ids, txt_ids, g)
-            ent = dict(graph=graph, out=out, ws=ws, rope=rope, times=(self._t1000, self._g1000))
-            # hand the buffers over: the next eager forward / capture allocates its own
-            self._ws_key = self._rope_key = None
-            self._t1000 = self._g1000 = None
+            ent = dict(graph=graph, out=out, buf=buf)
+            self._buf = _Buffers()                           # hand the buffers over: the next eager forward / capture allocates its own
         graphs[key] = ent                                     # (re)insert as most recently used
-        t1000, g1000 = ent["times"]
-        t1000.copy_((t.to(torch.bfloat16) * 1000).float())
-        if g is not None:
-            g1000.copy_((g.to(torch.bfloat16) * 1000).float())
+        ent["buf"].set_times(t, g, self.device)               # the entry's own time buffers (same B: the key holds the shapes)
         ent["graph"].replay()
         return ent["out"]
 

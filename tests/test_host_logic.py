@@ -189,7 +189,7 @@ def test_timestep_rounding_chain():
             for t in flow_sigmas(n, seq)[1]:
                 t32 = torch.tensor(float(t), dtype=torch.float32)
                 ref = (t32.to(torch.bfloat16) / 1000).to(torch.bfloat16) * 1000            # pipeline, then transformer
-                ours = torch.tensor(model_timestep(float(t))).to(torch.bfloat16) * 1000   # what FluxTransformerHIP._set_times does
+                ours = torch.tensor(model_timestep(float(t))).to(torch.bfloat16) * 1000   # what flux._Buffers.set_times does
                 assert float(ref) == float(ours)
                 n_diff += float(ref) != float((t32 / 1000).to(torch.bfloat16) * 1000)     # the naive chain is NOT the same
     assert n_diff > 50
